@@ -22,6 +22,13 @@ processes, before this process touches the GPU).  Camera streams are
 sharded (stream s -> rank s // 32), no collective on the data path (weak
 scaling); rank timings are reduced with a MAX (rvs_amd.shard.timed_job).
 
+A plain run sets up, warms up (--warmup steps, the conv autotuner, --warm-runs
+runs of the schedule), times the --steps steps, writes the last step's outputs
+when --dump-outputs DIR is given, and prints the line.  --full adds every
+other measurement of the line, each a run of its own after the timed region:
+the device-only rerun, the steady-state rate, the conv roofline, the pair-1
+rate, the secondary legs (bench_extra.py) and the CPU baseline.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -54,6 +61,59 @@ WORLD_POINTS = [[-3.5, 5.0], [3.5, 5.0], [3.5, 30.0], [-3.5, 30.0]]
 METRIC = "end-to-end frames/sec @1080p (preproc+YOLOv8n+SORT), 1/2/4/8 MI355X"
 PMC_TRAFFIC = os.path.join(REPO, "profiles", "r06", "pmc_traffic.json")
 LIB = os.path.join(REPO, "road-vision-system_amd", "rvs_amd", "librvhip.so")
+
+
+# A run of any length holds a bounded set of 1080p buffers (199 MB per step
+# and kind at 32 streams): the default run's 60 + 5 input frames, cycled by
+# longer runs (FramePool), and as many proc buffers (pipelined_run).
+FRAME_POOL = 65
+# untimed warm runs of the recorded schedule: at most this many steps in all,
+# so a long run's warm-up does not grow with --steps (a run longer than this
+# has none: its first-run costs are spread over that many steps)
+WARM_STEPS = 1000
+# --full: the legs after the timed region run over at most this many steps
+FULL_STEPS = 60
+
+
+class FramePool:
+    """frames[i] of an endless sequence over the generated frames: played
+    forward, then backward, then forward again (the objects keep moving
+    without a jump); i below the number of generated frames is frame i."""
+
+    def __init__(self, frames):
+        self.frames, self.n = frames, len(frames)
+
+    def __getitem__(self, i: int):
+        n = self.n
+        if i >= n:
+            i %= max(1, 2 * n - 2)
+            i = i if i < n else 2 * n - 2 - i
+        return self.frames[i]
+
+
+def pipelined_run(eng, frames, ts, **kw):
+    """PipelinedRun(eng, frames, ts, **kw) whose steps share FRAME_POOL proc
+    buffers (step k writes buffer k % FRAME_POOL; nothing in a run reads
+    them, and only the last FRAME_POOL steps' outs[k]["proc"] then hold their
+    own step's frames).  The constructor allocates one proc buffer per step
+    with torch.empty, 199 MB each at 32 streams; while it runs, torch.empty
+    hands out the shared buffers for that shape."""
+    from rvs_amd.schedule import PipelinedRun
+    shape, real, ring, calls = (eng.S, eng.H, eng.W, 3), torch.empty, [], [0]
+
+    def empty(*size, **opts):
+        if size != (shape,) or opts.get("dtype") != torch.uint8:
+            return real(*size, **opts)
+        if len(ring) < FRAME_POOL:
+            ring.append(real(*size, **opts))
+        calls[0] += 1
+        return ring[(calls[0] - 1) % FRAME_POOL]
+
+    torch.empty = empty
+    try:
+        return PipelinedRun(eng, frames, ts, **kw)
+    finally:
+        torch.empty = real
 
 
 def bench_config():
@@ -117,6 +177,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the pair-1 rate and the secondary legs (configs[1], configs[4], "
                          "host-fed NV12; bench_extra.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other measurement of the line: "
+                         "the device-only rerun, the steady-state rate, the conv roofline "
+                         "(--conv-timing), the pair-1 rate and the secondary legs (--no-secondary) "
+                         "and the CPU baseline (--no-cpu-baseline); a plain run stops after the "
+                         "timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region write what its last step handed back "
+                         "(dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--job", default=None,
                     help="module:Class of a stand-in rank job (CPU rehearsal of the rank logic "
                          "with gloo; tests/test_shard_gloo.py)")
@@ -203,8 +272,9 @@ class BenchJob:
         lanes, pair = (1, 1) if seq else (2, max(self.unit_sizes))
         self.eng = RoadVisionEngine(self.cfg, self.S, (H, W), device=dev, tmax=args.tmax,
                                     lanes=lanes, pair=pair)
-        self.frames = frames if frames is not None else road_frames(
-            self.S, self.Wm + self.K, H, W, device=dev, stream_offset=rank_streams(self.S, rank).start)
+        self.frames = FramePool(frames if frames is not None else road_frames(
+            self.S, min(self.Wm + self.K, FRAME_POOL), H, W, device=dev,
+            stream_offset=rank_streams(self.S, rank).start))
         self.ts = torch.tensor([[f / 30.0] * self.S for f in range(self.Wm + self.K)],
                                dtype=torch.float64, device=dev)
         self.units = self.S * self.K
@@ -220,6 +290,7 @@ class BenchJob:
         self.tags = (1, 2)       # rv_trace_marker tags around the timed region
         self.t_device_only = None  # local time of the device-only rerun
         self.sort_saved = None   # SORT state the timed region starts from
+        self.last_proc = None    # sequential mode: the last step's proc frames
         torch.cuda.synchronize()
 
     def warmup(self):
@@ -251,11 +322,7 @@ class BenchJob:
             from rvs_amd.handback import Record
             self.records = [Record(self.S, eng.detector.max_det, self.dev) for _ in range(K)]
         else:
-            from rvs_amd.schedule import PipelinedRun
-            self.runner = PipelinedRun(eng, [self.frames[Wm + k] for k in range(K)],
-                                       [self.ts[Wm + k] for k in range(K)], mode=a.exec_mode,
-                                       sync=a.sync, units=self.unit_sizes)
-            self.records = self.runner.records
+            self._record_schedule()
             # the SORT state is restored after the warm runs (and before the
             # device-only rerun), so every timed run sees exactly the tracks
             # the warm-up steps left
@@ -275,12 +342,33 @@ class BenchJob:
             # (first run 40.0-40.3k against 41.7-41.8k frames/s after one
             # more untimed run with the thread, tools/consumer_ab.py, r04)
             tags, self.tags = self.tags, (9, 10)
-            for _ in range(a.warm_runs):
+            for _ in range(min(a.warm_runs, WARM_STEPS // K)):
                 self.run()
                 self.sync()
             self.tags = tags
             eng.tracker.state[0].copy_(self.sort_saved)
         torch.cuda.synchronize()
+
+    def _record_schedule(self):
+        """The pipelined schedule of the K steps after the warm-up steps."""
+        K, Wm, a = self.K, self.Wm, self.args
+        self.runner = pipelined_run(self.eng, [self.frames[Wm + k] for k in range(K)],
+                                    [self.ts[Wm + k] for k in range(K)], mode=a.exec_mode,
+                                    sync=a.sync, units=self.unit_sizes)
+        self.records = self.runner.records
+
+    def shorten(self, steps: int):
+        """Cut the job to its first `steps` steps (the legs of --full after a
+        long timed region): the schedule is recorded again over them."""
+        self.K = steps
+        self.units = self.S * steps
+        self.records = self.records[:steps]
+        if self.runner is not None:
+            self.runner.close()
+            spec = self.args.units if self.args.units in ("even", "ends", "ramp") else "ends"
+            # the engine's forward batch was sized for the long run's units
+            self.unit_sizes = unit_sizes(steps, min(self.args.pair, self.eng.pair), spec)
+            self._record_schedule()
 
     def _consume(self, wait_step, materialise: bool, ready=None):
         """The consumer: every step's List[Detection] per stream, built as
@@ -339,10 +427,11 @@ class BenchJob:
         else:
             evs = []
             for k in range(self.K):
-                self.eng.step(self.frames[self.Wm + k], self.ts[self.Wm + k], self.records[k])
+                out = self.eng.step(self.frames[self.Wm + k], self.ts[self.Wm + k], self.records[k])
                 e = torch.cuda.Event()
                 e.record()
                 evs.append(e)
+            self.last_proc = out["proc"]
             wait = lambda k: evs[k].synchronize()  # noqa: E731
             ready = lambda k: evs[k].query()  # noqa: E731
         self.issue_s = time.perf_counter() - t0
@@ -390,6 +479,54 @@ def rank_job_again(job, device) -> dict:
     finally:
         job.consume = consume
         job.tags = tags
+
+
+DUMP_PROC_SAMPLES = 1 << 20  # proc-frame values kept by --dump-outputs (4 MB as float32)
+
+
+def dump_outputs(job, out_dir: str, rank: int = 0) -> None:
+    """--dump-outputs: what the last step of the timed region handed to its
+    caller (PipelinedRun.outs[K - 1]; a sequential run: the last step()), as
+    out_dir/<name>.npy (rank r > 0: <name>.rank<r>.npy).  From the step's
+    pinned host record, every array (S, max_det) with the rows past a
+    stream's detection count zeroed:
+      det_count (S,), boxes_xyxy (S, max_det, 4), conf, cls_id  float32
+      track_id, distance_m, speed_kmh                           float64
+        (track_id / distance_m / speed_kmh None -> -1)
+    and of the step's proc frames (S, H, W, 3) u8, 199 MB at 32 x 1080p, a
+    fixed sample: proc_sample_index (flat indices drawn once with seed 0,
+    float64) and proc_sample (the frames' values there, float32).  Call
+    after the timed region and before anything else runs on the engine."""
+    torch.cuda.synchronize()
+    n, rows = job.records[-1].arrays()
+    n = np.clip(n.astype(np.int64), 0, rows.shape[1])
+    valid = np.arange(rows.shape[1])[None, :] < n[:, None]
+
+    def col(name, dtype, none=None):
+        v = rows[name].astype(dtype)
+        if none is not None:
+            v = np.where(none(rows[name]), dtype(-1), v)
+        return np.where(valid, v, dtype(0))
+
+    proc = job.runner.procs[-1] if job.runner is not None else job.last_proc
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(proc.numel(), (min(DUMP_PROC_SAMPLES, proc.numel()),), generator=g)
+    idx = idx.sort().values
+    arrays = {
+        "det_count": n.astype(np.float32),
+        "boxes_xyxy": np.stack([col(k, np.float32) for k in ("x1", "y1", "x2", "y2")], -1),
+        "conf": col("conf", np.float32),
+        "cls_id": col("cls", np.float32),
+        "track_id": col("track_id", np.float64, lambda t: t < 0),
+        "distance_m": col("dist", np.float64, np.isnan),
+        "speed_kmh": col("speed", np.float64, np.isnan),
+        "proc_sample_index": idx.numpy().astype(np.float64),
+        "proc_sample": proc.reshape(-1)[idx.to(proc.device)].float().cpu().numpy(),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f".rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), np.ascontiguousarray(a))
 
 
 def _union_ms(t0, t1) -> float:
@@ -758,8 +895,8 @@ def steady_state(job, mult: int = 3) -> dict:
 def _cpu_baseline_leg(args, rank: int, world: int, cfg) -> dict:
     """The CPU baseline, on rank 0 only, after the ranks' last barrier (the
     other ranks are done with the GPU by then): at N > 1 the scaling line
-    keeps its baseline too.  {} when disabled or not rank 0."""
-    if rank != 0 or args.no_cpu_baseline or args.cpu_frames <= 0:
+    keeps its baseline too.  {} without --full, when disabled or not rank 0."""
+    if not args.full or rank != 0 or args.no_cpu_baseline or args.cpu_frames <= 0:
         return {}
     budget = host_cpu_budget()
     workers = args.cpu_workers or budget["cpus"]
@@ -808,7 +945,7 @@ def pair1_rate(job, rank: int, dev) -> dict:
     configuration run alone (r04)."""
     a = job.args
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(job.K), "--warmup", str(job.Wm),
-           "--pair", "1", "--units", "even", "--no-secondary", "--no-cpu-baseline",
+           "--pair", "1", "--units", "even", "--full", "--no-secondary", "--no-cpu-baseline",
            "--conv-timing", "none", "--streams", str(job.S), "--gpus", "1"]
     if a.exec_mode != "native":
         cmd += ["--exec", a.exec_mode]
@@ -877,13 +1014,20 @@ def main(argv=None):
         handback["detections_per_step"] = round(cons["detections"] / K, 1)
         handback["materialise_ms_per_step"] = round(cons["busy_s"] / K * 1e3, 3)
         handback["consumer_done_after_device_ms"] = round((cons["end"] - job.device_end) * 1e3, 3)
+    if args.dump_outputs:
+        dump_outputs(job, args.dump_outputs, rank)
+    # everything below that runs the device again is --full only: a plain run
+    # ends with the timed region
+    full = args.full
+    if full and K > FULL_STEPS:
+        job.shorten(FULL_STEPS)
     # the same K steps again without the consumer, from the same SORT state:
     # the device-only rate, and the steady state from its per-step completions
-    t2 = rank_job_again(job, dev) if job.consume == "consume" else None
-    sort_phase = _sort_phase_report()
+    t2 = rank_job_again(job, dev) if full and job.consume == "consume" else None
+    sort_phase = _sort_phase_report() if full else None
     job.t_device_only = t2["local_s"] if t2 is not None else None
-    steady = steady_state(job) if world == 1 else {}
-    roof = conv_roofline(job, args.conv_timing) if args.conv_timing != "none" else None
+    steady = steady_state(job) if full and world == 1 else {}
+    roof = conv_roofline(job, args.conv_timing) if full and args.conv_timing != "none" else None
     if roof and "algorithmic_gflop_per_step" in roof:
         # the conv family's FLOPs over the whole step of the timed region (every
         # other stage included): the chip-level rate the bench delivers
@@ -933,12 +1077,14 @@ def main(argv=None):
         if sort_phase is not None:
             res["sort_phase"] = sort_phase
         res["device_only"] = {"value": round(t2["value"], 2),
-                              "ms_per_step": round(t2["elapsed_s"] / K * 1e3, 4),
+                              "ms_per_step": round(t2["elapsed_s"] / job.K * 1e3, 4),
                               "note": "the same K steps timed again without the Detection "
                                       "consumer, from the same SORT state (trace window: marker "
                                       "tags 7-8)"}
     res.update(steady)
-    if world == 1 and not args.no_secondary:
+    if job.K != K:
+        res["full_legs_steps"] = job.K  # the legs of --full ran over the first FULL_STEPS steps
+    if full and world == 1 and not args.no_secondary:
         if args.exec_mode != "sequential" and P > 1:
             try:
                 res["pair1"] = pair1_rate(job, rank, dev)

@@ -159,7 +159,7 @@ def test_bench_gpus_flag_spawns_the_ranks(tmp_path, capfd, monkeypatch):
     monkeypatch.setenv("OMP_NUM_THREADS", "2")
     S, F = 2, 3
     rc = bench.main(["--gpus", "2", "--streams", str(S), "--steps", str(F), "--warmup", "0",
-                     "--cpu-frames", "1", "--cpu-workers", "1",
+                     "--full", "--cpu-frames", "1", "--cpu-workers", "1",
                      "--job", "test_shard_gloo:_CpuJob"])
     assert rc == 0
     lines = [ln for ln in capfd.readouterr().out.splitlines() if ln.startswith("{")]
@@ -202,3 +202,15 @@ def test_pick_pair_divides_the_step_count():
     assert bench.pick_pair(10, 4) == 2 and bench.pick_pair(9, 4) == 3
     assert bench.pick_pair(7, 4) == 1 and bench.pick_pair(5, 1) == 1 and bench.pick_pair(3, 0) == 1
     assert bench.parse_args([]).pair == 4
+
+
+def test_full_legs_units_fit_any_forward_batch():
+    """bench.py --full after a long run records its legs over FULL_STEPS
+    steps on the engine the long run built: whatever pair that run's step
+    count gave (1 for a prime count), the units sum to FULL_STEPS and none
+    exceeds the pair."""
+    import bench
+    for pair in (1, 2, 3, 4):
+        for spec in ("even", "ends", "ramp"):
+            u = bench.unit_sizes(bench.FULL_STEPS, pair, spec)
+            assert sum(u) == bench.FULL_STEPS and 1 <= min(u) and max(u) <= pair, (pair, spec, u)

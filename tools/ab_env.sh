@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG:-ab}
 mkdir -p "$OUT"
 for v in $VALS; do
   export "$VAR=$v"
-  RV_CONV_DEBUG=1 timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps ${STEPS:-40} \
+  RV_CONV_DEBUG=1 timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps ${STEPS:-40} \
     > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err"
   echo "$VAR=$v $(python3 -c "import json;d=json.load(open('$OUT/bench_$v.json'));print(d['value'], d['ms_per_step'], d['roofline']['conv_ms_per_step'])")"
   [ "${SKIP_TRACE:-0}" = 1 ] && continue

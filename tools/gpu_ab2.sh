@@ -19,7 +19,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   while IFS=';' read -r label envs; do
     [ -z "$label" ] && continue
     f=$OUT/${label}_$r.json
-    env $envs timeout -k 10 400 python -u bench.py --gpus 1 --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline \
+    env $envs timeout -k 10 400 python -u bench.py --gpus 1 --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline \
       --no-secondary $BENCH_ARGS > $f 2> ${f%.json}.err || { tail -n 30 ${f%.json}.err; exit 1; }
     echo "$label #$r: $(python3 -c "
 import json;d=json.load(open('$f'))

@@ -18,7 +18,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   tail -2 "$O/pytest_gpu.log"
   $T 120 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || exit 1
 fi
-RV_CONV_TABLE=$O/tab $T 500 python bench.py --steps 20 --tune-save "$O/tune.json" \
+RV_CONV_TABLE=$O/tab $T 500 python bench.py --full --steps 20 --tune-save "$O/tune.json" \
   > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cut -c1-300 "$O/bench.json"
 TAG=${O#gpurun_out/}/prof TUNE=$O/tune.json STEPS=20 CONV_TIMING=both BENCH_ARGS=--no-secondary \

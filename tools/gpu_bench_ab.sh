@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${TAG:-bab}
 mkdir -p "$OUT"
 STEPS=${STEPS:-20}
-COMMON="--gpus 1 --steps $STEPS --warmup 5 --no-cpu-baseline --no-secondary --conv-timing none"
+COMMON="--gpus 1 --full --steps $STEPS --warmup 5 --no-cpu-baseline --no-secondary --conv-timing none"
 timeout -k 10 400 python -u bench.py $COMMON --tune-save $OUT/tune.json > $OUT/tune_run.json 2> $OUT/tune_run.err \
   || { tail -n 30 $OUT/tune_run.err; exit 1; }
 echo "tune run: $(python3 -c "import json;d=json.load(open('$OUT/tune_run.json'));print(d['value'], d['ms_per_step'])")"

@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG:-prof}
 STEPS=${STEPS:-60}
 mkdir -p "$OUT"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/raw" -o trace -- \
-  python3 bench.py --tune-load "$TUNE" --warmup 1 --steps "$STEPS" --no-cpu-baseline \
+  python3 bench.py --full --tune-load "$TUNE" --warmup 1 --steps "$STEPS" --no-cpu-baseline \
   --conv-timing ${CONV_TIMING:-none} ${BENCH_ARGS:-} > "$OUT/bench_profiled.json" \
   2> "$OUT/bench_profiled.err" || exit $?
 KT=$(find "$OUT/raw" -name "*kernel_trace.csv" | head -1)
