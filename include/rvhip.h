@@ -176,22 +176,14 @@ int rv_yolo_destroy(void* handle);
 /* RV_YOLO_OPT_HEAD_STREAMS (default 1): the P3 / P4 Detect heads run on two
  * side streams of the handle (forked / joined with events) so they overlap
  * the rest of the neck; 0 keeps them on the caller's stream (a pipelined
- * caller whose stages already overlap).  The environment variable
- * RV_HEAD_STREAMS=0/1 overrides it. */
+ * caller whose stages already overlap). */
 #define RV_YOLO_OPT_HEAD_STREAMS 4
 /* RV_YOLO_OPT_FUSE_CV1 (default 1): model.3 and model.4.cv1 (the C2f's
  * first 1x1) run as one launch -- the 1x1 works on model.3's output tile in
  * LDS, so that map never reaches HBM; bit-identical to the two launches.
  * Raw parity forwards with RV_YOLO_OPT_RAW_UNFUSED keep them separate. */
 #define RV_YOLO_OPT_FUSE_CV1 5
-/* RV_YOLO_OPT_HEAD_CHAIN (default 0): candidate forwards of the YOLOv8n-
- * shaped bf16 head run each branch's last 1x1 conv inside its 3x3 conv's
- * launch (box: + DFL, class: + sigmoid / first maximum) and form the
- * candidates in one small kernel; the same candidates as the decode
- * kernel, whose head features and logits then never reach HBM.  Raw
- * forwards (raw_out) keep the decode kernel.  Off by default: on MI355X the
- * chained 3x3 launches cost what the decode saves. */
-#define RV_YOLO_OPT_HEAD_CHAIN 6
+/* Option 6 (the chained Detect head) is retired and must not be reused. */
 /* RV_YOLO_OPT_C2F_TAP_PAIRS (default 1): the fused hidden-width-16 C2f chain
  * (model.2 of YOLOv8n) runs its 3x3 convs on tap pairs -- two taps' 16
  * channels per 32-deep MFMA k-step, 5 k-steps instead of 9 half-zero ones;

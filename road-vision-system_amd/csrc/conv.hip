@@ -1,4 +1,5 @@
-// YOLOv8 conv / pooling / head-decode kernels for gfx950.
+// YOLOv8 conv kernels for gfx950 (the SPPF pool is sppf.hip, the Detect
+// decode detect.hip).
 //
 // Reference: the YOLOv8 graph Ultralytics runs inside model.predict
 // (src/detect/yolo_ultralytics.py:28-35; Conv = conv + fused BN + SiLU,
@@ -6,13 +7,12 @@
 // [Cout_pad16][ky][kx][Cin_pad32] bf16 so every MFMA operand fragment is one
 // 16-byte load.
 //
-// conv_mfma_kernel is an implicit GEMM  D[cout][pixel] = W[cout][k] * X[k][pixel]
-// on v_mfma_f32_16x16x32_bf16 with A = weights (staged through LDS, shared by
-// the 4 waves of a workgroup) and B = input pixels (16 B per lane straight from
-// HBM/L2: lane l reads 8 channels of pixel l&15).  The accumulator layout puts
-// 4 consecutive output channels of one pixel in each lane, so the epilogue
-// (bias, SiLU, residual add, bf16 pack) stores 8 contiguous bytes per lane into
-// each destination view (concat slice and/or nearest-2x upsampled copy).
+// The kernels, in the order launch_conv tries them: conv1x1_direct_kernel
+// (1x1 convs with a virtual concat input, and tuned 1x1 layers),
+// conv_patch_kernel (the LDS-staged implicit GEMM every k in {1,3},
+// s in {1,2} layer of the plans runs) and conv_mfma_kernel, the generic
+// fallback for the shapes rv_conv_bf16 supports but the patch kernel has no
+// configuration for (a 1x1 stride-2 conv, images of Hin*Win >= 2^24 pixels).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -21,10 +21,17 @@
 
 namespace rv {
 
+// conv_mfma_kernel, the generic fallback: an implicit GEMM
+// D[cout][pixel] = W[cout][k] * X[k][pixel] on v_mfma_f32_16x16x32_bf16 with
+// no LDS.  The accumulator layout puts 4 consecutive output channels of one
+// pixel in each lane, so the epilogue (bias, SiLU, residual add, bf16 pack)
+// stores 8 contiguous bytes per lane into each destination view (concat
+// slice and/or nearest-2x upsampled copy).
 // Wave tile: MR x NR fragments of 16x16 (16*MR output channels x 16*NR
 // pixels).  A workgroup is 4 waves arranged WP (pixel groups) x WC (channel
 // groups); every wave streams its own A (weights, L1/L2-resident, shared by
-// the WP waves of a channel group) and B (input pixels) fragments straight
+// the WP waves of a channel group) and B (input pixels: 16 B per lane, lane l
+// reads 8 channels of pixel l&15) fragments straight from HBM/L2
 // into VGPRs, double-buffered one k-step ahead, so there is no LDS and no
 // barrier in the K loop: the loads of k-step s+1 are in flight while the
 // MFMAs of k-step s issue.
@@ -325,21 +332,9 @@ static inline int xcd_grid(int want, int ntiles, bool persist) {
   return g >= 8 ? g & ~7 : g;
 }
 
-// cache-policy bits of the activation-patch DMA (A/B builds: 2 = nt)
-#ifndef RV_CONV_IN_AUX
-#define RV_CONV_IN_AUX 0
-#endif
-template <int AUX = 0>
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, void* lds, uint32_t voff, int soff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16,
-                                           (int)voff, soff, 0, AUX);
-}
-
-// Detect-head class score: exp + one v_rcp_f32 (no IEEE division
-// sequence); the decode, its raw output and the chained head epilogue
-// (conv_patch_kernel CHM = 3) all use this one function.
-__device__ __forceinline__ float head_sigmoid(float x) {
-  return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+                                           (int)voff, soff, 0, 0);
 }
 
 struct PatchGeo {
@@ -350,7 +345,6 @@ struct PatchGeo {
   int tiles_x, tiles_y;
   int p_bytes;     // pinst * 1024
   int fast;        // epilogue_fast applies (epi_fast)
-  int stagger;     // 8-wave form: waves 4-7 run each tile's epilogue one step late
 };
 
 // The common epilogue (one bf16 output view, no upsampled copy, optional
@@ -359,9 +353,8 @@ struct PatchGeo {
 // 24-bit multiply per pixel, each 16-channel fragment m in the instruction's
 // immediate offset -- no 64-bit address arithmetic per (pixel, fragment).
 static bool epi_fast(const ConvArgs& a) {
-  static const bool off = getenv("RV_EPI_SLOW") != nullptr;  // A/B: the generic epilogue
   const double px = (double)a.B * a.Ho * a.Wo;
-  return !off && !a.out_f32 && !a.out1 && !a.out0_up && !a.in8 && a.Cout % 16 == 0 && px < (1 << 23) &&
+  return !a.out_f32 && !a.out1 && !a.out0_up && !a.in8 && a.Cout % 16 == 0 && px < (1 << 23) &&
          a.out0_cs < 2048 && px * a.out0_cs * 2 < 2147483647.0 &&
          (!a.res || (a.res_cs < 2048 && px * a.res_cs * 2 < 2147483647.0));
 }
@@ -725,14 +718,11 @@ __device__ __forceinline__ void epilogue8(const ConvArgs& a, f32x4 (&acc)[MR][NR
 // so a resident weight slab (or a staged chunk of weights) is shared by 8
 // waves and the pixel tile is twice as large -- half the LDS-DMA bytes per
 // MFMA of the 4-wave form at the same occupancy (2 waves per SIMD).
-// CHM > 0 (ConvArgs::ch_w / ch_mode): a chained 1x1 conv Cout -> Cout on
-// the tile's output in LDS (bf16, one cout tile covering Cout): CHM 1 = a
-// C2f cv1 (SiLU, stored), 2 = a Detect box branch's last conv + DFL (four
-// distances per pixel stored), 3 = a Detect class branch's last conv +
-// sigmoid + first maximum (score, class per pixel stored): see chain_tile.
-template <int MR, int NR, int K, int S, bool RESW, bool F8, int NW = 4, int CHM = 0>
+// CH (ConvArgs::ch_w): a chained 1x1 conv Cout -> Cout on the tile's output
+// in LDS (bf16, one cout tile covering Cout) -- a C2f cv1 (SiLU, stored):
+// see chain_tile.
+template <int MR, int NR, int K, int S, bool RESW, bool F8, int NW = 4, bool CH = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(ConvArgs a, PatchGeo g) {
-  constexpr bool CH = CHM != 0;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int T2 = K * K;
   constexpr int BC = 16 * MR;
@@ -846,14 +836,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
   // (the wave's 16 NR pixels x Cout channels of the producer's bf16 output,
   // chunk-major [c][pixel][64 B], quarter swizzle by pixel)
   constexpr int CHN = (MR + 1) / 2;                 // 32-channel chunks of the chained input
-  constexpr int CHF = BC + 4;                       // CHM 2: floats per pixel row of the logit tile
   uint8_t* const ch_w_lds = (uint8_t*)(bias_lds + BC);
   float* const ch_b_lds = (float*)(ch_w_lds + (CH ? CHN * BC * 64 : 0));
   uint8_t* const ch_x_lds = (uint8_t*)(ch_b_lds + (CH ? BC : 0)) + wave * (CH ? CHN * NR * 16 * 64 : 0);
-  float* const ch_f_lds = (float*)((uint8_t*)(ch_b_lds + (CH ? BC : 0)) + NW * (CH ? CHN * NR * 16 * 64 : 0)) +
-                          wave * (CHM == 2 ? NR * 16 * CHF : 0);
   if constexpr (CH) {
-    static_assert(!F8 && K == 3, "chained 1x1: bf16 behind a 3x3 conv");
+    static_assert(!F8 && K == 3 && MR % 2 == 0, "chained 1x1: bf16 behind a 3x3 conv, fragment pairs");
     // BC / 16 DMA instructions per chunk (16 rows x 64 B each); the packed
     // 1x1 rows are CHN * 32 channels long (zero beyond Cout)
     for (int j = wave; j < CHN * (BC / 16); j += NW) {
@@ -864,13 +851,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
                                        (void*)(ch_w_lds + c * BC * 64 + jr * 1024), 16, 0, 0);
     }
     for (int i = tid; i < BC; i += 64 * NW) ch_b_lds[i] = a.ch_b[i];
-    if constexpr (MR % 2) {  // odd MR: the last chunk's upper half is k-padding, zero for good
-      for (int px = lane; px < NR * 16; px += 64) {
-        uint8_t* sl = ch_x_lds + ((CHN - 1) * NR * 16 + px) * 64;
-        *(uint4*)(sl + ((2 ^ swzq<false>(px)) << 4)) = make_uint4(0, 0, 0, 0);
-        *(uint4*)(sl + ((3 ^ swzq<false>(px)) << 4)) = make_uint4(0, 0, 0, 0);
-      }
-    }
   }
   // Patch and weight DMA through buffer resources (buffer_load ... lds):
   // every DMA instruction's per-lane byte offset is computed once -- per
@@ -953,23 +933,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
       // v_cndmask into it then waited for the previous buffer_load to read
       // its operand (a VMEM-read / VALU-write interlock per DMA); the common
       // path issues straight from the per-slot offset registers.
-#ifdef RV_DMA_SELECT_ALWAYS  // A/B: the r05 single path
-      if (true) {
-#else
       if (tail) {
-#endif
 #pragma unroll
         for (int it = 0; it < MAXP; ++it) {
           const int j = wave + NW * it;
           if (j < g.pinst)
-            dma16<RV_CONV_IN_AUX>(img_rsrc, P + j * 1024,
-                                  tail && ((tailbad >> it) & 1) ? kOOB : voff[it], c * 64);
+            dma16(img_rsrc, P + j * 1024, tail && ((tailbad >> it) & 1) ? kOOB : voff[it], c * 64);
         }
       } else {
 #pragma unroll
         for (int it = 0; it < MAXP; ++it) {
           const int j = wave + NW * it;
-          if (j < g.pinst) dma16<RV_CONV_IN_AUX>(img_rsrc, P + j * 1024, voff[it], c * 64);
+          if (j < g.pinst) dma16(img_rsrc, P + j * 1024, voff[it], c * 64);
         }
       }
       if constexpr (!RESW) dma_weights(c, P + g.p_bytes);
@@ -1124,22 +1099,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
 #endif
   int ti = walk.t0;  // tile of the current step
   int grp = 0;       // chunk group of the current step
-  // Stagger (8-wave form): the two waves of a SIMD are wave w and w + 4 of
-  // this block, and with one barrier per step they reach their MFMAs and
-  // their epilogue VALU together.  Waves 4-7 ("late") instead finish each
-  // tile at the start of the NEXT step, right after the barrier, with the
-  // sums still in their accumulators: on every SIMD one wave's epilogue
-  // (bias, SiLU, pack, stores) then runs beside its partner's MFMAs
-  // (MI355X_MICROARCH.md "Two waves per SIMD" item 9).  Same values, same
-  // stores: outputs are bit-identical.
-  // (not built for the 5x2 / 2x4 tiles: their extra epilogue site spills)
-  constexpr bool kStagger = NW == 8 && !(MR == 5 && NR == 2) && !(MR == 2 && NR == 4);
-  const bool late = kStagger && g.stagger && wave >= 4;  // wave is a scalar
-  bool pend = false;  // late waves: a finished tile (ptile) awaits its epilogue
-  int ptile = 0;
   constexpr bool kDefer = !F8 && !CH && MR * NR <= 10;
-  // epilogue of tile `tile` from acc; `pk`: pack only (stores after the
-  // barrier, epi_store)
+  // epilogue of tile `tile` from acc (kDefer tiles on the fast path: packed
+  // only, into ep; epi_store issues the stores after the barrier)
   // CH: the finished tile's producer values (bias, SiLU, bf16 -- what the
   // unfused conv stores) go to this wave's x tile instead of HBM, then the
   // chained 1x1 runs on them: per 32-channel chunk c ascending, A = its
@@ -1151,22 +1113,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
     if constexpr (CH) {
       f32x4 bl[MR];
       bias_tile(bl);
-      if constexpr (MR % 2) {  // odd MR: each lane stores its 4 channels (8 B) of every fragment
-#pragma unroll
-        for (int n = 0; n < NR; ++n) {
-          const int px = n * 16 + col;
-#pragma unroll
-          for (int m = 0; m < MR; ++m) {
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = acc[m][n][i] + bl[m][i];
-            if (a.act) silu4(v);
-            const int qq = 2 * (m & 1) + (quad >> 1);  // channels 16 (m & 1) + 4 quad of chunk m / 2
-            *(v2u32*)(ch_x_lds + ((m / 2) * NR * 16 + px) * 64 + ((qq ^ swzq<false>(px)) << 4) +
-                      (quad & 1) * 8) = v2u32{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
-          }
-        }
-      } else {
 #pragma unroll
       for (int n = 0; n < NR; ++n) {
         const int px = n * 16 + col;
@@ -1189,7 +1135,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
           *(v4u32*)(ch_x_lds + ((m / 2) * NR * 16 + px) * 64 + ((qq ^ swzq<false>(px)) << 4)) =
               v4u32{x0[0], x1[0], x0[1], x1[1]};
         }
-      }
       }
       f32x4 acc2[MR][NR];
 #pragma unroll
@@ -1220,96 +1165,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
       f32x4 bl2[MR];
 #pragma unroll
       for (int m = 0; m < MR; ++m) bl2[m] = *(const f32x4*)(ch_b_lds + m * 16 + quad * 4);
-      if constexpr (CHM == 1) {
-        ConvArgs a2 = a;
-        a2.act = 1;
-        a2.res = nullptr;
-        epilogue_fast<MR, NR>(a2, acc2, 0, pv, opx, quad, bl2);
-      } else if constexpr (CHM == 2) {
-        // box branch: 4 sides x 16 DFL bins (fragment m = side m).  The f32
-        // logits go to this wave's LDS rows, then 4 lanes per pixel take a
-        // side each: softmax expectation over its bins exactly as
-        // detect_decode_kernel computes it (same op order), and the pixel's
-        // four distances are stored as one f32x4
-        static_assert(MR == 4, "box branch: 4 sides of 16 bins");
-#pragma unroll
-        for (int n = 0; n < NR; ++n)
-#pragma unroll
-          for (int m = 0; m < MR; ++m)
-            *(f32x4*)(ch_f_lds + (n * 16 + col) * CHF + m * 16 + quad * 4) = acc2[m][n] + bl2[m];
-        const int pxl = lane >> 2, part = lane & 3;
-#pragma unroll
-        for (int n = 0; n < NR; ++n) {
-          const float* row = ch_f_lds + (n * 16 + pxl) * CHF + part * 16;
-          float v[16];
-#pragma unroll
-          for (int i = 0; i < 16; i += 4) {
-            const f32x4 q4 = *(const f32x4*)(row + i);
-            v[i] = q4[0];
-            v[i + 1] = q4[1];
-            v[i + 2] = q4[2];
-            v[i + 3] = q4[3];
-          }
-          float mx = -INFINITY;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) mx = fmaxf(mx, v[i]);
-          float sum = 0.f;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            v[i] = __expf(v[i] - mx);
-            sum += v[i];
-          }
-          const float rs = __builtin_amdgcn_rcpf(sum);
-          float e = 0.f;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) e += (float)i * (v[i] * rs);
-          const int base = lane & ~3;
-          const float d0 = __shfl(e, base), d1 = __shfl(e, base + 1), d2 = __shfl(e, base + 2),
-                      d3 = __shfl(e, base + 3);
-          // pixel pxl of fragment n: lane pxl holds its validity and index
-          const uint32_t o = (uint32_t)__shfl((int)opx[n], pxl);
-          const bool ok = __shfl((int)pv[n], pxl) != 0;
-          if (part == 0 && ok) *(f32x4*)((float*)a.out0 + (size_t)o * 4) = f32x4{d0, d1, d2, d3};
-        }
-      } else {
-        // class branch: sigmoid of every class, the first maximum in class
-        // order (lane scan over its classes m * 16 + 4 quad + i ascending,
-        // then the larger score / smaller class across the quads) -- the
-        // fixed decode's head_mfma_fixed selection; (score, class) stored
-#pragma unroll
-        for (int n = 0; n < NR; ++n) {
-          float best = -1.f;
-          int bc = 0;
-#pragma unroll
-          for (int m = 0; m < MR; ++m) {
-            const int co = m * 16 + quad * 4;
-            const f32x4 v = acc2[m][n] + bl2[m];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float sg = head_sigmoid(v[i]);
-              if (co + i < a.Cout && sg > best) {
-                best = sg;
-                bc = co + i;
-              }
-            }
-          }
-#pragma unroll
-          for (int off = 16; off < 64; off <<= 1) {
-            const float ob = __shfl_xor(best, off);
-            const int oc = __shfl_xor(bc, off);
-            if (ob > best || (ob == best && oc < bc)) {
-              best = ob;
-              bc = oc;
-            }
-          }
-          if (quad == 0 && pv[n])
-            *(v2u32*)((float*)a.out0 + (size_t)opx[n] * 2) =
-                v2u32{__float_as_uint(best), (uint32_t)bc};
-        }
-      }
+      ConvArgs a2 = a;
+      a2.act = 1;
+      a2.res = nullptr;
+      epilogue_fast<MR, NR>(a2, acc2, 0, pv, opx, quad, bl2);
     }
   };
-  auto finish = [&](int tile, EpiPend<MR, NR>& ep, bool pk) {
+  auto finish = [&](int tile, EpiPend<MR, NR>& ep) {
     const int b = tile / tiles_img;
     const int r = tile - b * tiles_img;
     const int ty = r / g.tiles_x, tx = r - (r / g.tiles_x) * g.tiles_x;
@@ -1322,18 +1184,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
       px[n] = tx * g.C + ocol[n];
       pv[n] = oin[n] && py[n] < a.Ho && px[n] < a.Wo;
     }
-#ifdef RV_EPI_SKIP
-    if (a.Cout == 12345) {  // timing experiment: keep the MFMAs live, skip the epilogue
-      float t = 0.f;
-#pragma unroll
-      for (int m = 0; m < MR; ++m)
-#pragma unroll
-        for (int n = 0; n < NR; ++n) t += acc[m][n][0] + acc[m][n][3];
-      ((float*)a.out0)[tid] = t;
-    }
-    if (true) {
-    } else
-#endif
     if constexpr (F8) {
       epilogue8<MR, NR>(a, acc, cout0, pv, pb, py, px, quad, bias, dq);
     } else if constexpr (CH) {
@@ -1347,14 +1197,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
       for (int n = 0; n < NR; ++n) opx[n] = __umul24((uint32_t)(b * a.Ho + py[n]), (uint32_t)a.Wo) + px[n];
       f32x4 bl[MR];
       bias_tile(bl);
-      if constexpr (kDefer) {
-        if (pk)
-          epi_pack<MR, NR>(a, acc, cout0, pv, opx, quad, bl, ep);
-        else
-          epilogue_fast<MR, NR>(a, acc, cout0, pv, opx, quad, bl);
-      } else {
+      if constexpr (kDefer)
+        epi_pack<MR, NR>(a, acc, cout0, pv, opx, quad, bl, ep);
+      else
         epilogue_fast<MR, NR>(a, acc, cout0, pv, opx, quad, bl);
-      }
     } else {
       f32x4 bl[MR];
       bias_tile(bl);
@@ -1369,10 +1215,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
   RV_PH(0);
   for (int s = 0; s < nsteps; ++s) {
     EpiPend<MR, NR> ep;
-    if (kStagger && pend) {  // late waves: the previous tile, before its accumulators are reset
-      finish(ptile, ep, false);
-      pend = false;
-    }
     if (grp == 0) {
 #pragma unroll
       for (int m = 0; m < MR; ++m)
@@ -1391,12 +1233,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
     // a finished tile's packed outputs, stored after the barrier (tiles whose
     // pack registers fit beside the compute registers without spills)
     if (last) {
-      if (late) {
-        pend = true;
-        ptile = ti;
-      } else {
-        finish(ti, ep, true);
-      }
+      finish(ti, ep);
       ti += walk.step;
       grp = 0;
       RV_PH(3);
@@ -1405,13 +1242,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_patch_kernel(Co
     }
     __syncthreads();
     if constexpr (kDefer) {
-      if (last && g.fast && !late) epi_store<MR, NR>(a, ep);  // the finished tile's stores (epi_pack)
+      if (last && g.fast) epi_store<MR, NR>(a, ep);  // the finished tile's stores (epi_pack)
     }
     RV_PH(4);
-  }
-  if (kStagger && pend) {
-    EpiPend<MR, NR> ep;
-    finish(ptile, ep, false);
   }
 #ifdef RV_PHASE_PROF
   if (lane == 0) {
@@ -1657,12 +1490,6 @@ static bool patch_geo(const ConvArgs& a, const ConvCfg& c, PatchGeo& g, size_t& 
   const int nch = conv_nch(a);
   g.G = std::max(1, std::min(c.G, nch));
   g.fast = epi_fast(a) ? 1 : 0;
-  // the 8-wave stagger (late waves finish a tile beside the partner's
-  // MFMAs): off by default -- measured no gain when built (r06b) and
-  // −1.6 % at the end of r06 (7 interleaved rounds, profiles/r06/session_ab
-  // r06zh / r06zi); RV_STAGGER=1 enables it
-  static const int stagger = getenv("RV_STAGGER") ? atoi(getenv("RV_STAGGER")) : 0;
-  g.stagger = stagger;
   // per-lane offset registers of the kernel (patch_maxit)
   const int maxit = (a.stride == 2 ? 6 : 2) * NR + 2;
   if (ceil_div(g.pinst, NW) > maxit) return false;
@@ -1670,35 +1497,20 @@ static bool patch_geo(const ConvArgs& a, const ConvCfg& c, PatchGeo& g, size_t& 
   // two stages: the next (tile, chunk group) streams in during the current one
   smem = (c.resw ? nch * wb : 0) + 2 * (size_t)g.G * (g.p_bytes + (c.resw ? 0 : wb)) +
          (a.in8 ? 0 : (size_t)16 * MR * 4);  // bf16: the block's bias
-  if (a.ch_w) {  // chained 1x1: its weights and bias, one x tile per wave (+ logit rows)
+  if (a.ch_w) {  // chained 1x1: its weights and bias, one x tile per wave
     const size_t chn = (MR + 1) / 2;
-    smem += chn * 16 * MR * 64 + (size_t)16 * MR * 4 + (size_t)NW * chn * NR * 16 * 64 +
-            (a.ch_mode == 2 ? (size_t)NW * NR * 16 * (16 * MR + 4) * 4 : 0);
+    smem += chn * 16 * MR * 64 + (size_t)16 * MR * 4 + (size_t)NW * chn * NR * 16 * 64;
   }
   return smem <= 160 * 1024;
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
-      n = p.multiProcessorCount;
-    else
-      n = 256;
-    (void)hipGetLastError();
-  }
-  return n;
-}
-
 // Every instantiation gets the full 160 KB dynamic-LDS cap once; resident
 // blocks per CU are cached per LDS size (per instantiation).
-template <int MR, int NR, int K, int S, bool RESW, bool F8 = false, int NW = 4, int CHM = 0>
+template <int MR, int NR, int K, int S, bool RESW, bool F8 = false, int NW = 4, bool CH = false>
 static int launch_patch_t(const ConvArgs& a, const PatchGeo& g, size_t smem, int persist,
                           hipStream_t s) {
   static bool attr = false;
-  auto fn = conv_patch_kernel<MR, NR, K, S, RESW, F8, NW, CHM>;
+  auto fn = conv_patch_kernel<MR, NR, K, S, RESW, F8, NW, CH>;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        160 * 1024);
@@ -1813,34 +1625,24 @@ constexpr bool patch_spills8(int MR, int NR, int K, int S, bool RESW) {
                     (S == 2 && !RESW && MR == 1 && NR == 2));
 }
 
-// chained-1x1 (CHM) instantiations: C2f cv1 behind a 64-channel 3x3 conv
-// (YOLOv8n model.3 -> model.4.cv1, mode 1, stride 2), the Detect box /
-// class branches' last convs behind their 3x3 (.1 -> .2: mode 2 with 64
-// channels, mode 3 with 80, stride 1); ch_tile_ok is the host-side check
-template <int MR, int NR, int CHM>
+// chained-1x1 (CH) instantiations: C2f cv1 behind a 64-channel 3x3 conv
+// (YOLOv8n model.3 -> model.4.cv1, stride 2); ch_tile_ok is the host-side
+// check
+template <int MR, int NR>
 constexpr bool ch_built() {
-  return NR <= 2 && ((CHM <= 2 && MR == 4) || (CHM == 3 && MR == 5));
+  return NR <= 2 && MR == 4;
 }
-static bool ch_tile_ok(int mr, int nr, int mode) {
-  return nr <= 2 && ((mode <= 2 && mr == 4) || (mode == 3 && mr == 5));
-}
+static bool ch_tile_ok(int mr, int nr) { return nr <= 2 && mr == 4; }
 template <int MR, int NR, bool RESW, int NW>
 static int launch_patch_ch(const ConvArgs& a, const PatchGeo& g, size_t smem, int persist,
                            hipStream_t s) {
-  if constexpr (ch_built<MR, NR, 1>()) {
-    if (a.ch_mode == 1 && a.k == 3 && a.stride == 2)
-      return launch_patch_t<MR, NR, 3, 2, RESW, false, NW, 1>(a, g, smem, persist, s);
-    if (a.ch_mode == 1 && a.k == 3 && a.stride == 1)
-      return launch_patch_t<MR, NR, 3, 1, RESW, false, NW, 1>(a, g, smem, persist, s);
+  if constexpr (ch_built<MR, NR>()) {
+    if (a.k == 3 && a.stride == 2)
+      return launch_patch_t<MR, NR, 3, 2, RESW, false, NW, true>(a, g, smem, persist, s);
+    if (a.k == 3 && a.stride == 1)
+      return launch_patch_t<MR, NR, 3, 1, RESW, false, NW, true>(a, g, smem, persist, s);
   }
-  if constexpr (ch_built<MR, NR, 2>())
-    if (a.ch_mode == 2 && a.k == 3 && a.stride == 1)
-      return launch_patch_t<MR, NR, 3, 1, RESW, false, NW, 2>(a, g, smem, persist, s);
-  if constexpr (ch_built<MR, NR, 3>())
-    if (a.ch_mode == 3 && a.k == 3 && a.stride == 1)
-      return launch_patch_t<MR, NR, 3, 1, RESW, false, NW, 3>(a, g, smem, persist, s);
-  set_error("conv_patch (chained 1x1 mode %d): no variant MR=%d NR=%d k=%d s=%d", a.ch_mode, MR, NR,
-            a.k, a.stride);
+  set_error("conv_patch (chained 1x1): no variant MR=%d NR=%d k=%d s=%d", MR, NR, a.k, a.stride);
   return RV_EINVAL;
 }
 
@@ -1905,9 +1707,10 @@ static const int kTiles[][2] = {{8, 2}, {8, 1}, {5, 2}, {5, 1}, {4, 4}, {4, 2}, 
                                 {2, 4}, {2, 2}, {2, 1}, {1, 4}, {1, 2}, {1, 1}};
 
 bool conv_cfg_ok(const ConvArgs& a, const ConvCfg& c) {
-  if (a.ch_w &&  // chained 1x1: the patch kernel's CHM form, one cout tile covering Cout
-      (c.kind == 1 || a.in8 || !ch_tile_ok(c.mr, c.nr, a.ch_mode) || 16 * c.mr < a.Cout || 16 * c.mr - a.Cout >= 16 || a.k != 3 || a.res || a.out1 || a.out0_up || a.g2_cout0 > 0 ||
-       vcat(a) || (a.ch_mode == 1 ? !epi_fast(a) : (!a.out_f32 || a.stride != 1))))
+  if (a.ch_w &&  // chained 1x1: the patch kernel's CH form, one cout tile covering Cout
+      (c.kind == 1 || a.in8 || !ch_tile_ok(c.mr, c.nr) || 16 * c.mr < a.Cout ||
+       16 * c.mr - a.Cout >= 16 || a.k != 3 || a.res || a.out1 || a.out0_up || a.g2_cout0 > 0 ||
+       vcat(a) || !epi_fast(a)))
     return false;
   if (c.kind == 1) return !a.in8 && direct_ok(a, c);
   if ((c.kind != 0 && c.kind != 2) || vcat(a)) return false;
@@ -2041,22 +1844,8 @@ static bool default_cfg(const ConvArgs& a, ConvCfg& best) {
 
 // returns 1 if launched (status in *st), 0 if the patch kernel does not apply
 static int try_launch_patch(const ConvArgs& a, hipStream_t s, int* st) {
-  static const char* force = getenv("RV_CONV_FORCE");  // "direct" or "MR,NR[,G,resw]"
-  if (force && strcmp(force, "direct") == 0) return 0;
   ConvCfg c{0, 0, 1, 0, 1};
-  if (force) {
-    int fm = 0, fn = 0, fg = 1, fr = 0;
-    if (sscanf(force, "%d,%d,%d,%d", &fm, &fn, &fg, &fr) >= 2) {
-      c = ConvCfg{fm, fn, fg, fr, 1};
-      if (conv_cfg_ok(a, c)) {
-        *st = launch_conv_cfg(a, c, s);
-        return 1;
-      }
-    }
-  }
   if (!default_cfg(a, c)) return 0;
-  static const int persist = getenv("RV_CONV_PERSIST") ? atoi(getenv("RV_CONV_PERSIST")) : 1;
-  c.persist = persist;
   static const int dbg = getenv("RV_CONV_DEBUG") ? atoi(getenv("RV_CONV_DEBUG")) : 0;
   if (dbg)
     fprintf(stderr, "[conv] %dx%d k%d s%d Cin %d Cout %d -> MR=%d NR=%d G=%d resw=%d\n", a.Ho, a.Wo,
@@ -2064,748 +1853,6 @@ static int try_launch_patch(const ConvArgs& a, hipStream_t s, int* st) {
   *st = launch_conv_cfg(a, c, s);
   return 1;
 }
-
-// ---------------------------------------------------------------------------
-// SPPF: three chained MaxPool2d(5, 1, 2) == clipped 5/9/13 windows.
-// One thread per (pixel, 8-channel group).
-// ---------------------------------------------------------------------------
-// One workgroup per (image, 8-channel group).  The clipped k x k max is
-// separable (the clipped window is a rectangle), so a horizontal pass writes
-// the row maxima for k = 5/9/13 to LDS and a vertical pass finishes them;
-// one thread per pixel, 8 channels (one 16-B vector) each.  bf16 max is
-// exact, so values stay bf16 throughout.
-constexpr int kSppfLds = 160 * 1024;
-
-__device__ __forceinline__ void bf8_to_f(const uint4 v, float (&f)[8]) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[2 * j] = __uint_as_float(w[j] << 16);
-    f[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ uint4 f_to_bf8(const float (&f)[8]) {
-  // inputs are bf16 values: truncation is exact
-  uint32_t w[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    w[j] = (__float_as_uint(f[2 * j]) >> 16) | (__float_as_uint(f[2 * j + 1]) & 0xFFFF0000u);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// 16-B vector <-> its lanes as f32: 8 bf16 values, or 16 fp8 codes (one
-// buffer scale, so the max over codes' values re-encodes exactly).
-template <bool F8>
-struct SppfVec {
-  static constexpr int N = F8 ? 16 : 8;
-  __device__ static void dec(const uint4 v, float (&f)[N]) {
-    if constexpr (F8) {
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f[4 * j] = __builtin_amdgcn_cvt_f32_fp8((int)w[j], 0);
-        f[4 * j + 1] = __builtin_amdgcn_cvt_f32_fp8((int)w[j], 1);
-        f[4 * j + 2] = __builtin_amdgcn_cvt_f32_fp8((int)w[j], 2);
-        f[4 * j + 3] = __builtin_amdgcn_cvt_f32_fp8((int)w[j], 3);
-      }
-    } else {
-      bf8_to_f(v, f);
-    }
-  }
-  __device__ static uint4 enc(const float (&f)[N]) {
-    if constexpr (F8) {
-      uint32_t w[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float q[4] = {f[4 * j], f[4 * j + 1], f[4 * j + 2], f[4 * j + 3]};
-        w[j] = f8_encode4(q, 1.f);
-      }
-      return make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-      return f_to_bf8(f);
-    }
-  }
-};
-
-template <bool F8>
-__global__ __launch_bounds__(256) void sppf_pool_kernel(uint8_t* __restrict__ buf, int B, int H,
-                                                        int W, int c) {
-  using V = SppfVec<F8>;
-  constexpr int NV = V::N, EB = F8 ? 1 : 2;
-  extern __shared__ __attribute__((aligned(16))) uint4 sp[];  // x, h5, h9, h13: [H*W] uint4 each
-  const int groups = c / NV;
-  const int b = blockIdx.x / groups, g = blockIdx.x - (blockIdx.x / groups) * groups;
-  const int cs = 4 * c * EB;  // pixel stride, bytes
-  const int HW = H * W;
-  uint4* xs = sp;
-  uint4* h5 = sp + HW;
-  uint4* h9 = sp + 2 * HW;
-  uint4* h13 = sp + 3 * HW;
-  uint8_t* img = buf + (size_t)b * HW * cs + g * 16;
-  for (int p = threadIdx.x; p < HW; p += 256) xs[p] = *(const uint4*)(img + (size_t)p * cs);
-  __syncthreads();
-  for (int p = threadIdx.x; p < HW; p += 256) {
-    const int y = p / W, x = p - (p / W) * W;
-    float a5[NV], a9[NV], a13[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) a5[j] = a9[j] = a13[j] = -INFINITY;
-    // the taps' LDS reads issued in two groups (7 + 6) ahead of their max
-    // chains (a branch around each read made every one a separate LDS round
-    // trip; all 13 at once doubled the VGPRs, which cost more beside the
-    // forward's other kernels than the round trips saved); out-of-map taps
-    // read the edge pixel instead, which the window always holds, so the
-    // max (the -inf padding of MaxPool2d) is unchanged
-#pragma unroll
-    for (int d0 = -6; d0 <= 6; d0 += 7) {
-      uint4 raw[7];
-#pragma unroll
-      for (int d = d0; d < d0 + 7 && d <= 6; ++d) raw[d - d0] = xs[y * W + min(max(x + d, 0), W - 1)];
-#pragma unroll
-      for (int d = d0; d < d0 + 7 && d <= 6; ++d) {
-        float f[NV];
-        V::dec(raw[d - d0], f);
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-          a13[j] = fmaxf(a13[j], f[j]);
-          if (d >= -4 && d <= 4) a9[j] = fmaxf(a9[j], f[j]);
-          if (d >= -2 && d <= 2) a5[j] = fmaxf(a5[j], f[j]);
-        }
-      }
-    }
-    h5[p] = V::enc(a5);
-    h9[p] = V::enc(a9);
-    h13[p] = V::enc(a13);
-  }
-  __syncthreads();
-  for (int p = threadIdx.x; p < HW; p += 256) {
-    const int y = p / W, x = p - (p / W) * W;
-    float a5[NV], a9[NV], a13[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) a5[j] = a9[j] = a13[j] = -INFINITY;
-    // column pass, the same way: each map's taps read first, edge rows
-    // standing in for the out-of-map ones
-    auto col_max = [&](const uint4* hm, int r, float (&acc)[NV]) {
-#pragma unroll
-      for (int d0 = -r; d0 <= r; d0 += 7) {
-        uint4 rv[7];
-#pragma unroll
-        for (int d = d0; d < d0 + 7 && d <= r; ++d) rv[d - d0] = hm[min(max(y + d, 0), H - 1) * W + x];
-#pragma unroll
-        for (int d = d0; d < d0 + 7 && d <= r; ++d) {
-          float f[NV];
-          V::dec(rv[d - d0], f);
-#pragma unroll
-          for (int j = 0; j < NV; ++j) acc[j] = fmaxf(acc[j], f[j]);
-        }
-      }
-    };
-    col_max(h13, 6, a13);
-    col_max(h9, 4, a9);
-    col_max(h5, 2, a5);
-    uint8_t* o = img + (size_t)p * cs;
-    *(uint4*)(o + c * EB) = V::enc(a5);
-    *(uint4*)(o + 2 * c * EB) = V::enc(a9);
-    *(uint4*)(o + 3 * c * EB) = V::enc(a13);
-  }
-}
-
-template <bool F8>
-static int launch_sppf_t(uint8_t* buf, int B, int H, int W, int c, hipStream_t s) {
-  const size_t smem = (size_t)H * W * 64;  // 4 x 16 B per pixel
-  const int nv = F8 ? 16 : 8;
-  if (c % nv != 0 || smem > kSppfLds) {
-    set_error("sppf: c=%d / map %dx%d unsupported by the LDS pool", c, H, W);
-    return RV_EINVAL;
-  }
-  static bool attr = false;
-  if (!attr && smem > 64 * 1024) {  // only raise the cap when a map needs it
-    // best effort: a failure surfaces as the launch error reported below
-    (void)hipFuncSetAttribute((const void*)sppf_pool_kernel<F8>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kSppfLds);
-    (void)hipGetLastError();
-    attr = true;
-  }
-  sppf_pool_kernel<F8><<<B * (c / nv), 256, smem, s>>>(buf, B, H, W, c);
-  return launch_status("sppf_pool");
-}
-
-int launch_sppf_pool(bf16_t* buf, int B, int H, int W, int c, hipStream_t s) {
-  return launch_sppf_t<false>((uint8_t*)buf, B, H, W, c, s);
-}
-
-int launch_sppf_pool_fp8(uint8_t* buf, int B, int H, int W, int c, hipStream_t s) {
-  return launch_sppf_t<true>(buf, B, H, W, c, s);
-}
-
-// ---------------------------------------------------------------------------
-// Detect head decode: DFL softmax-expectation, dist2bbox (xywh) * stride,
-// class sigmoid; Ultralytics non_max_suppression candidate filter.
-// ---------------------------------------------------------------------------
-struct HeadLevels {
-  HeadLevel lv[4];
-  int start[5];  // first anchor of each level
-  int blk[5];    // first 64-anchor block of each level
-  int nlv;
-};
-
-// One 256-thread workgroup per 64 consecutive anchors of one level: their
-// (64 x cs) f32 head logits are one contiguous span, staged into LDS with
-// coalesced 16-B loads at a padded row stride (cs + 4 floats: rows 20 banks
-// apart, conflict-free fragment reads).  Four lanes share an anchor: lane
-// part p takes the DFL side p (softmax expectation over REG bins) and the
-// classes p, p+4, ...; the quad then combines the four sides and the
-// first-max class with lane shuffles.
-//
-// FUSED: the head's last 1x1 convs (cv2.i.2: 4*REG box logits, cv3.i.2: nc
-// class logits, no activation) run here on MFMA from the level's bf16
-// features (L.feat, [box feats | class feats]) straight into the LDS logits
-// tile, so the f32 logits never touch HBM (L.logits, when non-null, still
-// receives them: the parity tests read it).  Wave w computes anchors
-// 16w..16w+15 of the block: box fragments m = 0..REG/4-1, class fragments
-// after them; B fragments are 16-B loads of one anchor's 8 channels, A
-// fragments 16-B loads of the packed [cout][cin_pad32] weights (L2-resident).
-// Class score: exp + one v_rcp_f32 (no IEEE division sequence).  The raw
-// output and the candidate filter use this same function, so the scores NMS
-// sees are the scores in `raw`.
-// (head_sigmoid: defined with the patch kernel's chained head epilogue)
-
-// The fused head's MFMA section with compile-time trip counts (KB box /
-// KC class 32-channel k-steps, NCF class fragments: YOLOv8n's head is
-// KB = 2, KC = 3, NCF = 5): every A / B fragment load of the wave is issued
-// before the first MFMA, so the wave waits out one L2 latency instead of
-// one per (fragment, k-step) -- the runtime-bound loops compiled to a
-// load / s_waitcnt vmcnt(0) / MFMA chain.  Same k order and sums as the
-// generic loops (bit-identical logits).  The weight fragments (23 x 16 B
-// per lane) are loaded by head_weights once per level and stay in VGPRs
-// while the block walks its anchor tiles: per 16-anchor wave tile they were
-// 4.6x the feature bytes, all of it L2 -> CU traffic.
-template <int REG, int KB, int KC, int NCF>
-__device__ __forceinline__ void head_weights(const HeadLevel& L, uint4 (&Ab)[KB][REG / 4],
-                                             uint4 (&Ac)[KC][NCF]) {
-  constexpr int MB = REG / 4;
-  const int lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
-  constexpr int cinb = KB * 32, cinc = KC * 32;
-#pragma unroll
-  for (int k = 0; k < KB; ++k)
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-      Ab[k][m] = *(const uint4*)(L.w_box + (size_t)(m * 16 + col) * cinb + k * 32 + quad * 8);
-#pragma unroll
-  for (int k = 0; k < KC; ++k)
-#pragma unroll
-    for (int m = 0; m < NCF; ++m)
-      Ac[k][m] = *(const uint4*)(L.w_cls + (size_t)(m * 16 + col) * cinc + k * 32 + quad * 8);
-}
-
-// one 16-anchor wave tile's feature fragments (B operands): box channels,
-// then class channels of anchor r0 + 16 wave + col
-template <int REG, int KB, int KC>
-__device__ __forceinline__ void head_feats(const HeadLevel& L, int b, int HW, int r0, int na,
-                                           uint4 (&Bb)[KB], uint4 (&Bc)[KC]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, quad = lane >> 4;
-  const int an0 = wave * 16 + col;
-  const bool ok = an0 < na;
-  const bf16_t* fp = L.feat + ((size_t)b * HW + r0 + (ok ? an0 : 0)) * L.feat_cs + quad * 8;
-#pragma unroll
-  for (int k = 0; k < KB; ++k)
-    Bb[k] = ok && k * 32 + quad * 8 < L.cin_b ? *(const uint4*)(fp + k * 32) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-  for (int k = 0; k < KC; ++k)
-    Bc[k] = ok && k * 32 + quad * 8 < L.cin_c ? *(const uint4*)(fp + 4 * REG + k * 32)
-                                              : make_uint4(0, 0, 0, 0);
-}
-
-template <int REG, int KB, int KC, int NCF>
-__device__ __forceinline__ void head_mfma_fixed(const HeadLevel& L, const uint4 (&Ab)[KB][REG / 4],
-                                                const uint4 (&Ac)[KC][NCF], const uint4 (&Bb)[KB],
-                                                const uint4 (&Bc)[KC], float* lg, int nc,
-                                                float& best_out, int& bc_out) {
-  constexpr int MB = REG / 4;
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63, col = lane & 15, quad = lane >> 4;
-  float* row = lg + (size_t)(wave * 16 + col) * (L.cs + 4);
-  {
-    f32x4 acc[MB];
-#pragma unroll
-    for (int m = 0; m < MB; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < KB; ++k)
-#pragma unroll
-      for (int m = 0; m < MB; ++m)
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, Ab[k][m]),
-                                                         __builtin_bit_cast(bf16x8, Bb[k]), acc[m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      const int co = m * 16 + quad * 4;
-      *(f32x4*)(row + co) = acc[m] + *(const f32x4*)(L.b_box + co);
-    }
-  }
-  {
-    f32x4 acc[NCF];
-#pragma unroll
-    for (int m = 0; m < NCF; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < KC; ++k)
-#pragma unroll
-      for (int m = 0; m < NCF; ++m)
-        acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, Ac[k][m]),
-                                                         __builtin_bit_cast(bf16x8, Bc[k]), acc[m], 0, 0, 0);
-    // the class scores never go to LDS: lane quad q holds classes
-    // m * 16 + 4 q + i of its anchor (ascending in (m, i)), so a scan keeps
-    // the lane's first maximum and two cross-quad steps (larger score, then
-    // smaller class) give the anchor's first maximum -- the (score, class)
-    // of a scan over all nc in order.  Same value per class as the LDS path
-    // (acc + bias, then head_sigmoid).
-    float best = -1.f;
-    int bc = 0;
-#pragma unroll
-    for (int m = 0; m < NCF; ++m) {
-      const int co = m * 16 + quad * 4;
-      const f32x4 v = acc[m] + *(const f32x4*)(L.b_cls + co);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float sg = head_sigmoid(v[i]);
-        if (co + i < nc && sg > best) {
-          best = sg;
-          bc = co + i;
-        }
-      }
-    }
-#pragma unroll
-    for (int off = 16; off < 64; off <<= 1) {
-      const float ob = __shfl_xor(best, off);
-      const int oc = __shfl_xor(bc, off);
-      if (ob > best || (ob == best && oc < bc)) {
-        best = ob;
-        bc = oc;
-      }
-    }
-    best_out = best;
-    bc_out = bc;
-  }
-}
-
-
-template <int REG, bool FUSED, int KB = 0, int KC = 0, int NCF = 0, int NCT = 0>
-__global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B, int nc,
-                                                            float conf, float* __restrict__ raw,
-                                                            Cand* __restrict__ cand, int cap,
-                                                            int* __restrict__ seg_n, int nblk,
-                                                            int tpb) {
-  extern __shared__ __attribute__((aligned(16))) float lg[];  // [64][cs + 4]
-  __shared__ int wcnt[4];
-  const int b = blockIdx.y;
-  constexpr bool kFixed = FUSED && KC > 0;
-  uint4 Ab[kFixed ? KB : 1][REG / 4], Ac[kFixed ? KC : 1][kFixed ? NCF : 1];
-  uint4 Bb[kFixed ? KB : 1], Bc[kFixed ? KC : 1];  // the current tile's features
-  int wl = -1;       // level whose head weights are in Ab / Ac
-  bool pre = false;  // Bb / Bc already hold this tile's features
-  float hbest = -1.f;  // fixed head: the lane's anchor's best class score / class
-  int hbc = 0;
-  // The block walks anchor tiles blockIdx.x * tpb .. + tpb - 1 (64 anchors
-  // each; tpb > 1 only for the fixed fused head, whose weight fragments then
-  // stay in registers).  Every lg read of a tile precedes the block barrier
-  // before its candidate write-out, and a wave writes only its own 16 rows,
-  // so the next tile's MFMA section may overwrite the tile in place.
-  for (int t = 0; t < tpb; ++t) {
-    // block -> (level, first anchor in level).  Only compile-time indices
-    // into the by-value argument: a dynamic index would copy it to scratch.
-    const int blk = blockIdx.x * tpb + t;
-    if (blk >= nblk) break;  // block-uniform
-    int l = 0, A = h.start[1], lstart = 0, lblk = 0;
-    HeadLevel L = h.lv[0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i) {
-      if (i < h.nlv) A = h.start[i + 1];
-      if (i < h.nlv && blk >= h.blk[i]) {
-        l = i;
-        L = h.lv[i];
-        lstart = h.start[i];
-        lblk = h.blk[i];
-      }
-    }
-    const int HW = L.H * L.W;
-    const int r0 = (blk - lblk) * 64;
-    const int na = min(64, HW - r0);
-    const int tid = threadIdx.x;
-    const int cs4 = L.cs / 4, ls4 = cs4 + 1;  // row length / LDS row stride in float4
-    if constexpr (kFixed) {
-      if (l != wl) {
-        head_weights<REG, KB, KC, NCF>(L, Ab, Ac);
-        wl = l;
-      }
-      if (!pre) head_feats<REG, KB, KC>(L, b, HW, r0, na, Bb, Bc);
-      head_mfma_fixed<REG, KB, KC, NCF>(L, Ab, Ac, Bb, Bc, lg, nc, hbest, hbc);
-      // the next tile's features stream in under this tile's decode (same
-      // level only; a level change loads them at the top of its iteration)
-      pre = t + 1 < tpb && blk + 1 < nblk && r0 + 64 < HW;
-      if (pre) head_feats<REG, KB, KC>(L, b, HW, r0 + 64, min(64, HW - r0 - 64), Bb, Bc);
-      __syncthreads();
-    } else if constexpr (FUSED) {
-      constexpr int MB = REG / 4;  // box fragments (4*REG couts)
-      const int wave = tid >> 6, lane = tid & 63, col = lane & 15, quad = lane >> 4;
-      const int an0 = wave * 16 + col;  // this lane's anchor (B column / D column)
-      const bool ok = an0 < na;
-      const bf16_t* fp = L.feat + ((size_t)b * HW + r0 + (ok ? an0 : 0)) * L.feat_cs + quad * 8;
-      const int ncf = (nc + 15) / 16;  // class fragments
-      float* lrow = lg + (size_t)an0 * (L.cs + 4);
-      // box: K = cin_b (multiple of 32)
-      {
-        f32x4 acc[MB];
-#pragma unroll
-        for (int m = 0; m < MB; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int cinp = (L.cin_b + 31) & ~31;
-        for (int k = 0; k < cinp; k += 32) {
-          const bool kv = ok && k + quad * 8 < L.cin_b;
-          const uint4 bv = kv ? *(const uint4*)(fp + k) : make_uint4(0, 0, 0, 0);
-          const bf16x8 Bf = __builtin_bit_cast(bf16x8, bv);
-#pragma unroll
-          for (int m = 0; m < MB; ++m) {
-            const bf16x8 Af = __builtin_bit_cast(
-                bf16x8, *(const uint4*)(L.w_box + (size_t)(m * 16 + col) * cinp + k + quad * 8));
-            acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Af, Bf, acc[m], 0, 0, 0);
-          }
-        }
-        // lane holds couts m*16 + quad*4 + i of anchor `col` of this wave
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-          const int co = m * 16 + quad * 4;
-          const f32x4 bb = *(const f32x4*)(L.b_box + co);
-          *(f32x4*)(lg + (size_t)(wave * 16 + col) * (L.cs + 4) + co) = acc[m] + bb;
-        }
-      }
-      // classes: K = cin_c, couts nc (padded to 16)
-      {
-        const int cinp = (L.cin_c + 31) & ~31;
-        for (int m0 = 0; m0 < ncf; m0 += 5) {  // up to 5 fragments (80 classes) per pass
-          f32x4 acc[5];
-#pragma unroll
-          for (int m = 0; m < 5; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-          for (int k = 0; k < cinp; k += 32) {
-            const bool kv = ok && k + quad * 8 < L.cin_c;
-            const uint4 bv = kv ? *(const uint4*)(fp + 4 * REG + k) : make_uint4(0, 0, 0, 0);
-            const bf16x8 Bf = __builtin_bit_cast(bf16x8, bv);
-#pragma unroll
-            for (int m = 0; m < 5; ++m) {
-              if (m0 + m >= ncf) break;
-              const bf16x8 Af = __builtin_bit_cast(
-                  bf16x8,
-                  *(const uint4*)(L.w_cls + (size_t)((m0 + m) * 16 + col) * cinp + k + quad * 8));
-              acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Af, Bf, acc[m], 0, 0, 0);
-            }
-          }
-#pragma unroll
-          for (int m = 0; m < 5; ++m) {
-            if (m0 + m >= ncf) break;
-            const int co = (m0 + m) * 16 + quad * 4;  // class index (bias padded to 16)
-            const f32x4 bb = *(const f32x4*)(L.b_cls + co);
-            float* d = lg + (size_t)(wave * 16 + col) * (L.cs + 4) + 4 * REG + co;
-            const f32x4 v = acc[m] + bb;
-            // the last fragment may run past nc: keep the padding out of the row
-            if (co + 3 < nc) {
-              *(f32x4*)d = v;
-            } else {
-              for (int i = 0; i < 4; ++i)
-                if (co + i < nc) d[i] = v[i];
-            }
-          }
-        }
-      }
-      (void)lrow;
-      __syncthreads();
-      if (L.logits_out) {  // parity/debug copy of the logits (coalesced rows)
-        f32x4* dst = (f32x4*)(L.logits_out + ((size_t)b * HW + r0) * L.cs);
-        for (int i = tid; i < na * cs4; i += 256) {
-          const int row = i / cs4, c4 = i - (i / cs4) * cs4;
-          dst[i] = ((const f32x4*)lg)[row * ls4 + c4];
-        }
-      }
-    } else {
-      const f32x4* src = (const f32x4*)(L.logits + ((size_t)b * HW + r0) * L.cs);
-      // 8 loads in flight per thread before any LDS store (a plain copy loop
-      // would wait out one HBM latency per element)
-      for (int i0 = tid; i0 < na * cs4; i0 += 8 * 256) {
-        f32x4 v[8];  // native vectors (a float4 struct array would live in scratch)
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int i = i0 + u * 256;
-          v[u] = i < na * cs4 ? src[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int i = i0 + u * 256;
-          if (i < na * cs4) {
-            const int row = i / cs4, c4 = i - (i / cs4) * cs4;
-            ((f32x4*)lg)[row * ls4 + c4] = v[u];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    const int an = tid >> 2, part = tid & 3;
-    const bool live = an < na;
-    const float* px = lg + (live ? an : 0) * (L.cs + 4);
-    // DFL side `part`
-    float d;
-    {
-      float v[REG];
-      float mx = -INFINITY;
-      // the side's REG logits are 16-B aligned in the row (cs + 4 floats,
-      // a multiple of 4): ds_read_b128s
-#pragma unroll
-      for (int i = 0; i < REG; i += 4) {
-        const f32x4 q = *(const f32x4*)(px + part * REG + i);
-        v[i] = q[0];
-        v[i + 1] = q[1];
-        v[i + 2] = q[2];
-        v[i + 3] = q[3];
-      }
-#pragma unroll
-      for (int i = 0; i < REG; ++i) mx = fmaxf(mx, v[i]);
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < REG; ++i) {
-        v[i] = __expf(v[i] - mx);
-        sum += v[i];
-      }
-      // softmax probabilities by one reciprocal (v_rcp_f32, <= 1 ulp from
-      // v / sum; the decode tolerance is 2e-3 px)
-      const float rs = __builtin_amdgcn_rcpf(sum);
-      float e = 0.f;
-#pragma unroll
-      for (int i = 0; i < REG; ++i) e += (float)i * (v[i] * rs);
-      d = e;
-    }
-    // first maximum of the sigmoid scores.  The fixed head (NCT > 0) found
-    // it in registers (head_mfma_fixed: lane (col, quad) of the MFMA layout
-    // holds anchor col's result); otherwise lane part scans classes part,
-    // part + 4, ... in LDS and the quad reduction picks the larger score,
-    // then the smaller class.
-    const float* pc = px + 4 * REG;
-    float best = -1.f;
-    int bc = 0;
-    if constexpr (NCT > 0) {
-      best = __shfl(hbest, (tid & 63) >> 2);
-      bc = __shfl(hbc, (tid & 63) >> 2);
-    } else {
-      for (int c = part; c < nc; c += 4) {
-        const float sg = head_sigmoid(pc[c]);
-        if (sg > best) {
-          best = sg;
-          bc = c;
-        }
-      }
-#pragma unroll
-      for (int off = 1; off < 4; off <<= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oc = __shfl_xor(bc, off);
-        if (ob > best || (ob == best && oc < bc)) {
-          best = ob;
-          bc = oc;
-        }
-      }
-    }
-    const int base = tid & ~3;
-    const float d0 = __shfl(d, base), d1 = __shfl(d, base + 1), d2 = __shfl(d, base + 2),
-                d3 = __shfl(d, base + 3);
-    const int r = r0 + (live ? an : 0);
-    const int a = lstart + r;
-    const int y = r / L.W, x = r - (r / L.W) * L.W;
-    const float ax = (float)x + 0.5f, ay = (float)y + 0.5f;
-    const float x1 = ax - d0, y1 = ay - d1, x2 = ax + d2, y2 = ay + d3;
-    const float cx = (x1 + x2) / 2.0f * L.stride, cy = (y1 + y2) / 2.0f * L.stride;
-    const float w = (x2 - x1) * L.stride, hh = (y2 - y1) * L.stride;
-    if (NCT == 0 && raw && live) {  // (the fixed head runs without raw / logits_out)
-      for (int c = part; c < nc; c += 4)
-        raw[((size_t)b * (4 + nc) + 4 + c) * A + a] = head_sigmoid(pc[c]);
-      const float bxv = part == 0 ? cx : (part == 1 ? cy : (part == 2 ? w : hh));
-      raw[((size_t)b * (4 + nc) + part) * A + a] = bxv;
-    }
-    // Candidates go to this block's own 64-slot segment of the image's list
-    // (slot = segment * 64 + rank, ranks in anchor order) and the segment's
-    // count to seg_n: no cross-block atomics (same-address device atomics
-    // from thousands of waves serialise for ~100 us).
-    const bool pass = live && part == 0 && cand && best > conf;
-    const unsigned long long m = __ballot(pass);
-    const int wave = tid >> 6;
-    if ((tid & 63) == 0) wcnt[wave] = __popcll(m);
-    __syncthreads();
-    if (!cand) continue;
-    int base0 = blk * 64;
-    for (int w2 = 0; w2 < wave; ++w2) base0 += wcnt[w2];
-    if (tid == 0) seg_n[(size_t)b * nblk + blk] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-    if (pass) {
-      const int i = base0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      if (i < cap) {
-        const float hw = w / 2.0f, hh2 = hh / 2.0f;  // xywh2xyxy
-        Cand c;
-        c.x1 = cx - hw;
-        c.y1 = cy - hh2;
-        c.x2 = cx + hw;
-        c.y2 = cy + hh2;
-        c.score = best;
-        c.cls = bc;
-        c.anchor = a;
-        c.pad = 0;
-        cand[(size_t)b * cap + i] = c;
-      }
-    }
-  }
-}
-
-// The chained head's last step (ConvArgs::ch_mode 2 / 3 wrote, per level
-// pixel, the four DFL distances and the best class (score, class)): one
-// wave per 64-anchor segment of one image -- dist2bbox * stride,
-// xywh2xyxy and the conf filter with the expressions of
-// detect_decode_kernel, candidates in the same segmented layout and anchor
-// order (ballot ranks), so its output equals the fixed decode's.
-__global__ __launch_bounds__(256) void head_combine_kernel(HeadCombine h, int B, float conf,
-                                                           Cand* __restrict__ cand, int cap,
-                                                           int* __restrict__ seg_n, int nblk) {
-  const int b = blockIdx.y;
-  const int lane = threadIdx.x & 63;
-  const int blk = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  if (blk >= nblk) return;
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (i < h.nlv && blk >= h.blk[i]) l = i;
-  // compile-time selection of the level's fields (no dynamic index into
-  // the by-value argument)
-  const float* bx = h.bx[0];
-  const float* sc = h.sc[0];
-  int W = h.W[0], HW = h.H[0] * h.W[0], lstart = h.start[0], lblk = h.blk[0];
-  float stride = h.stride[0];
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (i == l) {
-      bx = h.bx[i];
-      sc = h.sc[i];
-      W = h.W[i];
-      HW = h.H[i] * h.W[i];
-      lstart = h.start[i];
-      lblk = h.blk[i];
-      stride = h.stride[i];
-    }
-  const int r0 = (blk - lblk) * 64;
-  const bool live = r0 + lane < HW;
-  const int r = r0 + (live ? lane : 0);
-  const f32x4 d = *(const f32x4*)(bx + ((size_t)b * HW + r) * 4);
-  const v2u32 q = *(const v2u32*)(sc + ((size_t)b * HW + r) * 2);
-  const float best = __uint_as_float(q[0]);
-  const int bc = (int)q[1];
-  const int a = lstart + r;
-  const int y = r / W, x = r - (r / W) * W;
-  const float ax = (float)x + 0.5f, ay = (float)y + 0.5f;
-  const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
-  const float cx = (x1 + x2) / 2.0f * stride, cy = (y1 + y2) / 2.0f * stride;
-  const float w = (x2 - x1) * stride, hh = (y2 - y1) * stride;
-  const bool pass = live && best > conf;
-  const unsigned long long m = __ballot(pass);
-  if (lane == 0) seg_n[(size_t)b * nblk + blk] = __popcll(m);
-  if (pass) {
-    const int i = blk * 64 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (i < cap) {
-      const float hw = w / 2.0f, hh2 = hh / 2.0f;  // xywh2xyxy
-      Cand c;
-      c.x1 = cx - hw;
-      c.y1 = cy - hh2;
-      c.x2 = cx + hw;
-      c.y2 = cy + hh2;
-      c.score = best;
-      c.cls = bc;
-      c.anchor = a;
-      c.pad = 0;
-      cand[(size_t)b * cap + i] = c;
-    }
-  }
-}
-
-int launch_head_combine(const HeadCombine& h, int B, float conf, Cand* cand, int cand_cap,
-                        int* cand_n, hipStream_t s) {
-  const int nblk = h.blk[h.nlv];
-  if (!cand || !cand_n || cand_cap < nblk * 64) {
-    set_error("head combine: candidate buffers (cap %d < %d segments x 64)", cand_cap, nblk);
-    return RV_EINVAL;
-  }
-  head_combine_kernel<<<dim3(ceil_div(nblk, 4), B), 256, 0, s>>>(h, B, conf, cand, cand_cap, cand_n, nblk);
-  return launch_status("head_combine");
-}
-
-int decode_segments(const HeadLevel* lv, int nlv) {
-  int n = 0;
-  for (int i = 0; i < nlv; ++i) n += ceil_div(lv[i].H * lv[i].W, 64);
-  return n;
-}
-
-int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_max, float conf,
-                         float* raw, Cand* cand, int cand_cap, int* cand_n, hipStream_t s) {
-  if (nlv < 1 || nlv > 4 || reg_max != 16) {
-    set_error("detect decode: nlv=%d reg_max=%d unsupported", nlv, reg_max);
-    return RV_EINVAL;
-  }
-  HeadLevels h;
-  h.nlv = nlv;
-  h.start[0] = 0;
-  h.blk[0] = 0;
-  int cs = lv[0].cs;
-  for (int i = 0; i < nlv; ++i) {
-    h.lv[i] = lv[i];
-    h.start[i + 1] = h.start[i] + lv[i].H * lv[i].W;
-    h.blk[i + 1] = h.blk[i] + ceil_div(lv[i].H * lv[i].W, 64);
-    if (lv[i].cs != cs || cs % 4 != 0) {
-      set_error("detect decode: head channel strides differ / not a multiple of 4");
-      return RV_EINVAL;
-    }
-  }
-  const size_t smem = (size_t)64 * (cs + 4) * 4;
-  const bool fused = lv[0].feat != nullptr;
-  // YOLOv8n's fused head (every level: box 64 -> 64, class 80 -> 80): the
-  // compile-time MFMA section
-  // (it keeps the class scores in registers: no raw output, no logits copy)
-  bool fixed = fused && nc == 80 && raw == nullptr;
-  for (int i = 0; i < nlv && fixed; ++i)
-    fixed = lv[i].cin_b == 64 && lv[i].cin_c == 80 && lv[i].logits_out == nullptr;
-  static const bool fixed_env = !getenv("RV_DECODE_FIXED") || atoi(getenv("RV_DECODE_FIXED")) != 0;
-  fixed = fixed && fixed_env;
-  if (smem > 64 * 1024) {  // only raise the cap when the head needs it (large nc)
-    // best effort: a failure surfaces as the launch error reported below
-    (void)hipFuncSetAttribute(fused ? (const void*)detect_decode_kernel<16, true>
-                              : (const void*)detect_decode_kernel<16, false>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-  }
-  const int nblk = h.blk[nlv];
-  if (cand && cand_cap < nblk * 64) {
-    set_error("detect decode: cand_cap %d < %d segments x 64", cand_cap, h.blk[nlv]);
-    return RV_EINVAL;
-  }
-  if (fused) {
-    for (int i = 0; i < nlv; ++i)
-      if (lv[i].cs != 4 * reg_max + nc || lv[i].cin_b % 8 || lv[i].cin_c % 8 || lv[i].feat_cs % 8) {
-        set_error("fused head: bad level %d geometry", i);
-        return RV_EINVAL;
-      }
-    if (fixed) {
-      // anchor tiles per block: enough blocks to fill the chip several times
-      static const int tpb_env = getenv("RV_DECODE_TPB") ? atoi(getenv("RV_DECODE_TPB")) : 0;
-      int tpb = tpb_env > 0 ? tpb_env : 4;
-      while (tpb > 1 && (long)ceil_div(nblk, tpb) * B < 4L * num_cus()) --tpb;
-      detect_decode_kernel<16, true, 2, 3, 5, 80><<<dim3(ceil_div(nblk, tpb), B), 256, smem, s>>>(
-          h, B, nc, conf, raw, cand, cand_cap, cand_n, nblk, tpb);
-    } else {
-      detect_decode_kernel<16, true><<<dim3(nblk, B), 256, smem, s>>>(h, B, nc, conf, raw, cand,
-                                                                      cand_cap, cand_n, nblk, 1);
-    }
-  } else {
-    detect_decode_kernel<16, false><<<dim3(nblk, B), 256, smem, s>>>(h, B, nc, conf, raw, cand,
-                                                                     cand_cap, cand_n, nblk, 1);
-  }
-  return launch_status("detect_decode");
-}
-
 
 // One bf16 conv (k 1 or 3, pad k / 2, SiLU optional, optional bf16 residual
 // of the output's shape) through the production launcher, for layer tests:
@@ -2850,5 +1897,3 @@ extern "C" int rv_conv_bf16(const void* in, int B, int Hin, int Win, int Cin, in
   }
   return launch_conv(a, s);
 }
-namespace rv {
-}  // namespace rv

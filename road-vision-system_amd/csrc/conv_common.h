@@ -1,6 +1,7 @@
-// Device helpers shared by the conv kernels (conv.hip) and the stem /
-// conv0 kernels (stem.hip): operand vector types, bf16 packing, SiLU, the
-// raw buffer-resource constants and the fp8 encoder.
+// Helpers shared by the conv kernels (conv.hip), the stem / conv0 kernels
+// (stem.hip), the SPPF pool (sppf.hip) and the Detect decode (detect.hip):
+// operand vector types, bf16 packing, SiLU, the raw buffer-resource
+// constants, the fp8 encoder and the device's CU count.
 #pragma once
 #include "conv.h"
 
@@ -65,6 +66,22 @@ __device__ __forceinline__ uint32_t f8_encode4(const float (&v)[4], float inv_s)
   int w = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
   w = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w, true);
   return (uint32_t)w;
+}
+
+// Compute units of the current device (grid sizing of the persistent conv
+// kernels and of the fixed decode).
+inline int num_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
+      n = p.multiProcessorCount;
+    else
+      n = 256;
+    (void)hipGetLastError();
+  }
+  return n;
 }
 
 }  // namespace rv

@@ -84,10 +84,9 @@ extern "C" int rv_results_handback(const float* dets, const int* det_n, const in
   // kernel itself (one launch; the kernel's completion, which the caller's
   // event waits for, publishes the writes): no staging copy and no
   // dependent copy launch per step -- at the end of a pipelined run those
-  // two gaps separated every SORT launch of the drain.  RV_HANDBACK_DIRECT=0
-  // keeps the stage + hipMemcpyAsync form (A/B).
-  static const bool direct = !getenv("RV_HANDBACK_DIRECT") || atoi(getenv("RV_HANDBACK_DIRECT")) != 0;
-  if (host_dst && direct) {
+  // two gaps separated every SORT launch of the drain.  Host memory that is
+  // not registered (the ABI accepts it) takes the stage + hipMemcpyAsync form.
+  if (host_dst) {
     void* dptr = nullptr;
     if (hipHostGetDevicePointer(&dptr, host_dst, 0) == hipSuccess && dptr) {
       results_pack_kernel<<<ceil_div(n, 256), 256, 0, as_stream(stream)>>>(

@@ -249,12 +249,8 @@ extern "C" int rv_sched_event_sync(void* handle, int event) {
   RV_CHECK_ARG(g >= 0 && S->ev_gen[event] == g,
                "rv_sched_event_sync: event %d was not issued by the latest completed run (call it "
                "after rv_sched_run returned without error)", event);
-  // poll (default): query + short sleeps, so a waiting consumer never enters
-  // the runtime's blocking wait while another thread is still issuing;
-  // RV_SCHED_WAIT=sync: hipEventSynchronize
-  static const bool use_sync = getenv("RV_SCHED_WAIT") && !strcmp(getenv("RV_SCHED_WAIT"), "sync");
-  if (use_sync)
-    return hip_check(hipEventSynchronize(S->events[event]), "rv_sched hipEventSynchronize");
+  // poll: query + short sleeps, so a waiting consumer never enters the
+  // runtime's blocking wait while another thread is still issuing
   for (;;) {
     const hipError_t e = hipEventQuery(S->events[event]);
     if (e == hipSuccess) return RV_OK;

@@ -345,7 +345,6 @@ struct Model {
   int stem_x1 = 0;
   int head_streams = 1;            // RV_YOLO_OPT_HEAD_STREAMS
   int fuse_cv1 = 1;                // RV_YOLO_OPT_FUSE_CV1
-  int head_chain = 0;              // RV_YOLO_OPT_HEAD_CHAIN (measured neutral: DESIGN.md)
   int c2f_tap_pairs = 1;           // RV_YOLO_OPT_C2F_TAP_PAIRS
   std::vector<Buf> bufs;
   int nA = 0;
@@ -370,7 +369,6 @@ struct Model {
   int X0, X1, C2, X2, X3, C4, CAT14, X5, C6, CAT11, X7, C8, X8, SP, CAT20, C12, CAT17, C15,
       X15, C18, X18, C21, X21;
   int DA[3], DB[3], HD[3];
-  int BX[3], SC[3];  // chained head: DFL distances / (score, class) per pixel
 
   size_t ws_bytes(int B) const {
     size_t off = 0;
@@ -414,8 +412,6 @@ static void plan(Model& M) {
     M.DA[i] = M.newbuf("DA" + l, 3 + i, v.c2d + v.c3d);
     M.DB[i] = M.newbuf("DB" + l, 3 + i, v.c2d + v.c3d, false, true);  // bf16: the decode's features
     M.HD[i] = M.newbuf("HD" + l, 3 + i, 4 * v.reg + v.nc, true);
-    M.BX[i] = M.newbuf("BX" + l, 3 + i, 4, true);
-    M.SC[i] = M.newbuf("SC" + l, 3 + i, 2, true);
   }
   // one temp per bottleneck (its first conv's output): no buffer is ever
   // overwritten inside a forward, so every layer stays inspectable
@@ -642,7 +638,7 @@ struct Exec {
   // as ONE cout tile of its own width (box 64, class 80) reading the input
   // once, where the grouped launch's 64-wide tiles padded the class branch
   // to 128 (r04: P3 head 306 -> 260 us per 128-frame unit,
-  // profiles/r04/conv_table_eager_*).  RV_HEAD_PAIR=1 / 0 forces either.
+  // profiles/r04/conv_table_eager_*).
   void conv_pair(const std::string& n1, View in1, const std::string& n2, View in2, int li,
                  View o0) {
     if (status) return;
@@ -651,9 +647,7 @@ struct Exec {
     const ConvSpec& c1 = M->def.convs[i1];
     const ConvSpec& c2 = M->def.convs[i2];
     const View o2{o0.buf, o0.cs, o0.co + c1.cout};
-    static const int env = getenv("RV_HEAD_PAIR") ? atoi(getenv("RV_HEAD_PAIR")) : -1;
-    const bool pair = env >= 0 ? env != 0 : c1.f8;
-    if (!pair || in1.buf != in2.buf || in1.cs != in2.cs || c1.k != c2.k || c1.s != c2.s ||
+    if (!c1.f8 || in1.buf != in2.buf || in1.cs != in2.cs || c1.k != c2.k || c1.s != c2.s ||
         c1.act != c2.act || c1.cout % 64 != 0) {
       conv(n1, in1, li, o0);
       conv(n2, in2, li, o2);
@@ -695,42 +689,10 @@ struct Exec {
     ConvCfg probe{4, 1, 1, 1, 1, 0};
     a.ch_w = wptr(c2);
     a.ch_b = bptr(c2);
-    a.ch_mode = 1;
     if (!conv_cfg_ok(a, probe)) return false;
     // trace records: the two convs as the unfused plan runs them
     trace(i1, args(c1, in, li, mid, 0, none, 0, none), in, mid, 0, none, 0, none);
     const ConvArgs a2 = args(c2, mid, li + 1, o0, 0, none, 0, none);
-    trace(i2, a2, mid, o0, 0, none, 0, none);
-    launch(a, i1, flops_of(c1, a) + flops_of(c2, a2));
-    return true;
-  }
-
-  // The Detect head's branch of level li: its 3x3 conv n1 (input view in,
-  // nominal output `mid` -- never written) with its last 1x1 conv n2
-  // chained in the same launch (ch_mode 2: box, DFL distances to o0; 3:
-  // class, best (score, class) to o0).  probe_only: just report whether the
-  // shapes have a chained configuration.
-  bool head_chain(const std::string& n1, View in, int li, View mid, const std::string& n2,
-                  View o0, int mode, bool probe_only) {
-    if (status) return false;
-    const int i1 = M->def.find(n1), i2 = M->def.find(n2);
-    if (i1 < 0 || i2 < 0) return false;
-    const ConvSpec& c1 = M->def.convs[i1];
-    const ConvSpec& c2 = M->def.convs[i2];
-    if (c1.f8 || c2.f8 || c1.k != 3 || c1.s != 1 || c2.k != 1 || c2.cin != c1.cout ||
-        c2.cout != c1.cout || !c1.act || c2.act || c1.cout != (mode == 2 ? 64 : 80))
-      return false;
-    const View none{-1, 0, 0};
-    ConvArgs a = args(c1, in, li, o0, 0, none, 0, none);
-    a.ch_w = wptr(c2);
-    a.ch_b = bptr(c2);
-    a.ch_mode = mode;
-    if (!conv_cfg_ok(a, ConvCfg{mode == 2 ? 4 : 5, 1, 1, 1, 1, 0}) &&
-        !conv_cfg_ok(a, ConvCfg{mode == 2 ? 4 : 5, 1, 1, 0, 1, 0}))
-      return false;
-    if (probe_only) return true;
-    trace(i1, args(c1, in, li, mid, 0, none, 0, none), in, mid, 0, none, 0, none);
-    const ConvArgs a2 = args(c2, mid, li, o0, 0, none, 0, none);
     trace(i2, a2, mid, o0, 0, none, 0, none);
     launch(a, i1, flops_of(c1, a) + flops_of(c2, a2));
     return true;
@@ -1021,9 +983,6 @@ extern "C" int rv_yolo_set_option(void* h, int opt, int value) {
     case RV_YOLO_OPT_FUSE_CV1:
       M->fuse_cv1 = value != 0;
       return RV_OK;
-    case RV_YOLO_OPT_HEAD_CHAIN:
-      M->head_chain = value != 0;
-      return RV_OK;
     case RV_YOLO_OPT_C2F_TAP_PAIRS:
       M->c2f_tap_pairs = value != 0;
       return RV_OK;
@@ -1106,45 +1065,26 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
   M->fused.clear();
   M->li_base = part == 2 ? M->n_part1 : (part == 4 ? M->n_part1a : 0);
   // fused C2f chains (c2f.hip) unless a raw parity forward keeps every
-  // activation (RV_YOLO_OPT_RAW_UNFUSED) or RV_FUSE_C2F=0
-  static const bool c2f_env = !getenv("RV_FUSE_C2F") || atoi(getenv("RV_FUSE_C2F")) != 0;
-  const bool fuse_c2f = c2f_env && !f8 && M->fuse_c2f && !(raw_out && M->raw_unfused);
+  // activation (RV_YOLO_OPT_RAW_UNFUSED) or RV_YOLO_OPT_FUSE_C2F = 0
+  const bool fuse_c2f = !f8 && M->fuse_c2f && !(raw_out && M->raw_unfused);
   // the hidden-width-32 chains (model.4, model.15 of YOLOv8n) measured
   // faster unfused since the patch kernel's buffer-DMA / fast-epilogue work
   // (r03: 188 + 86 us per 128-frame unit fused, 142 + 79 unfused): only
   // the C = 16 chain (model.2 at P2, 122 fused vs 191 unfused) stays fused
-  // unless RV_FUSE_C2F32=1 or RV_YOLO_OPT_FUSE_C2F = 2
-  static const bool c2f32_env = getenv("RV_FUSE_C2F32") && atoi(getenv("RV_FUSE_C2F32")) != 0;
-  const bool fuse_c2f32 = fuse_c2f && (c2f32_env || M->fuse_c2f == 2);
+  // unless RV_YOLO_OPT_FUSE_C2F = 2
+  const bool fuse_c2f32 = fuse_c2f && M->fuse_c2f == 2;
   const int cat14 = v.h12 + v.c3, cat11 = v.c5 + v.c4, cat20 = v.h18 + v.c5,
             cat17 = v.h15 + v.h12;
   // The neck's two Upsample + Concat pairs (yolov8.yaml layers 10-11 and
   // 13-14): bf16 plans read the upsampled half of model.12.cv1's and
   // model.15.cv1's input straight from the half-resolution map (a virtual
   // concat, ConvArgs::split / in_up), so the 4x upsampled copies are never
-  // written; fp8 plans (patch kernel only) and RV_VCAT=0 materialise them
-  // into CAT11[0, c5) / CAT14[0, h12) as before.
-  static const bool vcat_env = !getenv("RV_VCAT") || atoi(getenv("RV_VCAT")) != 0;
-  const bool vcat = vcat_env && !f8;
+  // written; fp8 plans (patch kernel only) materialise them into
+  // CAT11[0, c5) / CAT14[0, h12).
+  const bool vcat = !f8;
   const View none{-1, 0, 0};
   const VIn vin12{View{M->CAT20, cat20, v.h18}, 1, View{M->CAT11, cat11, v.c5}, v.c5};
   const VIn vin15{View{M->CAT17, cat17, v.h15}, 1, View{M->CAT14, cat14, v.h12}, v.h12};
-  auto c2f12 = [&]() {
-    E.c2f("model.12", View{M->CAT11, cat11, 0}, 4, M->C12, v.h12, v.nb, false,
-          View{M->CAT17, cat17, v.h15}, 0, vcat ? none : View{M->CAT14, cat14, 0}, vcat ? 0 : 1,
-          false, false, vcat ? &vin12 : nullptr);
-  };
-  auto c2f15 = [&]() {
-    E.c2f("model.15", View{M->CAT14, cat14, 0}, 3, M->C15, v.h15, v.nb, false,
-          View{M->X15, v.h15, 0}, 0, View{-1, 0, 0}, 0, v.h15 / 2 == 16 ? fuse_c2f : fuse_c2f32,
-          false, vcat ? &vin15 : nullptr);
-  };
-  // where part 1 ends (parts 1 / 4 vs part 2): after model.15 (15, default),
-  // model.12 (12) or SPPF (9) (RV_FWD_SPLIT).  Part 1 is the busier half
-  // (its stream 70 % busy against 45 % in the r04 trace), but moving the
-  // top-down neck's C2f blocks into part 2 measured slower (three A/B
-  // triples, r04: 44.6-45.1k at 15, 43.9-45.2k at 12, 43.6-44.7k at 9)
-  static const int split = getenv("RV_FWD_SPLIT") ? atoi(getenv("RV_FWD_SPLIT")) : 15;
   int st;
   if (part != 2) {
   if (part != 4) {  // part 4 continues after model.2
@@ -1155,11 +1095,10 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
   const Conv0Q q0{(const int8_t*)qb, qs, qs + c0.cout, (const int32_t*)(qs + 2 * c0.cout)};
   // conv0 + model.1 fused (the P1 map stays in LDS) unless the caller asked
   // for the raw prediction with RV_YOLO_OPT_RAW_UNFUSED set (layer parity
-  // forwards keep every activation in the workspace) or RV_FUSE_STEM=0
-  static const bool stem_env = !getenv("RV_FUSE_STEM") || atoi(getenv("RV_FUSE_STEM")) != 0;
+  // forwards keep every activation in the workspace)
   const int i1 = M->def.find("model.1");
   const bool fuse_stem =
-      stem_env && !f8 && !(raw_out && M->raw_unfused) && c0.cout == 16 && v.c2 == 32 && i1 >= 0;
+      !f8 && !(raw_out && M->raw_unfused) && c0.cout == 16 && v.c2 == 32 && i1 >= 0;
   // the fused stem also runs model.2.cv1 (32 -> 32 1x1) from its registers
   // into the model.2 concat buffer when the shapes allow
   const int i2cv1 = M->def.find("model.2.cv1");
@@ -1234,16 +1173,14 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
   }  // part != 4
   // model.3 + model.4.cv1 in one launch (the chained 1x1: model.3's output
   // map is only ever read by model.4.cv1) unless a raw parity forward keeps
-  // every activation (RV_YOLO_OPT_RAW_UNFUSED), RV_YOLO_OPT_FUSE_CV1 = 0 or
-  // RV_FUSE_CV1=0
+  // every activation (RV_YOLO_OPT_RAW_UNFUSED) or RV_YOLO_OPT_FUSE_CV1 = 0
   {
-    static const bool cv1_env = !getenv("RV_FUSE_CV1") || atoi(getenv("RV_FUSE_CV1")) != 0;
     const bool f4 = v.c3 / 2 == 16 ? fuse_c2f : fuse_c2f32;
     const int c4 = v.c3 / 2;
     const int c4cs = E.c2f_will_fuse(c4, v.nm, f4, 0, View{-1, 0, 0}, View{M->CAT14, cat14, v.h12})
                          ? 2 * c4
                          : (2 + v.nm) * c4;
-    const bool chained = cv1_env && M->fuse_cv1 && !f8 && !(raw_out && M->raw_unfused) &&
+    const bool chained = M->fuse_cv1 && !f8 && !(raw_out && M->raw_unfused) &&
                          E.conv_chain("model.3", View{M->X2, v.c2, 0}, 2, View{M->X3, v.c3, 0},
                                       "model.4.cv1", View{M->C4, c4cs, 0});
     if (!chained) E.conv("model.3", View{M->X2, v.c2, 0}, 2, View{M->X3, v.c3, 0});
@@ -1264,70 +1201,47 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
   if (st) return st;
   E.conv("model.9.cv2", View{M->SP, 4 * sc, 0}, 5, View{M->CAT20, cat20, v.h18}, 0,
          vcat ? none : View{M->CAT11, cat11, 0}, vcat ? 0 : 1);
-  // head
-  if (split >= 12) c2f12();
-  if (split >= 15) c2f15();
+  // head: the top-down neck.  Part 1 ends after model.15: it is the busier
+  // half (its stream 70 % busy against 45 % in the r04 trace), but moving
+  // the top-down neck's C2f blocks into part 2 measured slower (three A/B
+  // triples, r04: 44.6-45.1k ending here, 43.9-45.2k after model.12,
+  // 43.6-44.7k after SPPF)
+  E.c2f("model.12", View{M->CAT11, cat11, 0}, 4, M->C12, v.h12, v.nb, false,
+        View{M->CAT17, cat17, v.h15}, 0, vcat ? none : View{M->CAT14, cat14, 0}, vcat ? 0 : 1,
+        false, false, vcat ? &vin12 : nullptr);
+  E.c2f("model.15", View{M->CAT14, cat14, 0}, 3, M->C15, v.h15, v.nb, false,
+        View{M->X15, v.h15, 0}, 0, View{-1, 0, 0}, 0, v.h15 / 2 == 16 ? fuse_c2f : fuse_c2f32,
+        false, vcat ? &vin15 : nullptr);
   if (E.status) return E.status;
   M->n_part1 = M->li_base + (int)M->launches.size();
   M->part1_B = B;
   M->part1_ws = ws;
   if (part == 1 || part == 4) return RV_OK;
   }  // part != 2
-  // the top-down neck's C2f blocks after the split run at the start of part 2
-  if (split < 12) c2f12();
-  if (split < 15) c2f15();
-  if (E.status) return E.status;
   // Detect head of level i: box (cv2) and class (cv3) branches, one grouped
   // launch per stage; the last 1x1 stage runs inside the decode kernel
-  // (RV_FUSE_HEAD=0: separate launches and f32 logits in HBM).  The P3 and
-  // P4 heads are forked onto side streams as soon as their input map exists,
-  // so they overlap the rest of the neck (small, latency-bound launches);
+  // (heads whose widths are not multiples of 8: separate launches and f32
+  // logits in HBM).  The P3 and P4 heads are forked onto side streams as
+  // soon as their input map exists, so they overlap the rest of the neck
+  // (small, latency-bound launches);
   // RV_YOLO_OPT_HEAD_STREAMS = 0 (a pipelined caller: its stages already
   // overlap, and two more streams per handle share the process's 4 hardware
   // queues -- r04: +3 % in the pipeline with the heads on the caller's
-  // stream) or RV_HEAD_STREAMS=0 / 1 (overrides) keeps everything on the
-  // caller's stream.
+  // stream) keeps everything on the caller's stream.
   const View P[3] = {View{M->X15, v.h15, 0}, View{M->X18, v.h18, 0}, View{M->X21, v.h21, 0}};
   const int dcs = v.c2d + v.c3d, hcs = 4 * v.reg + v.nc;
-  static const bool fuse_env = !getenv("RV_FUSE_HEAD") || atoi(getenv("RV_FUSE_HEAD")) != 0;
-  const bool fuse_head = fuse_env && v.c2d % 8 == 0 && v.c3d % 8 == 0;
-  static const int streams_env = getenv("RV_HEAD_STREAMS") ? atoi(getenv("RV_HEAD_STREAMS")) != 0 : -1;
-  const bool streams_on = streams_env >= 0 ? streams_env != 0 : M->head_streams != 0;
+  const bool fuse_head = v.c2d % 8 == 0 && v.c3d % 8 == 0;
   // profiled forwards time every launch alone (per-launch roofline), so the
   // heads stay on the caller's stream there; so do batches under 8, whose
   // few-us head launches gain less from the overlap than the fork / join
   // event round trips cost (batch 1, r05: 0.356 -> 0.308 ms device time per
   // forward, launch submission 284 -> 218 us, tools/c2_host.py)
-  const bool fork = streams_on && B >= 8 && M->side[0] && M->side[1] &&
+  const bool fork = M->head_streams && B >= 8 && M->side[0] && M->side[1] &&
                     !(M->prof.on && M->prof.n_fwd < M->prof.cap_fwd);
   const hipStream_t main_s = E.s;
-  // The chained head (RV_YOLO_OPT_HEAD_CHAIN; RV_HEAD_CHAIN=0/1 overrides):
-  // each branch's .1 conv runs its .2 1x1 on the tile in LDS and keeps only
-  // the DFL distances (box) / the best (score, class) (class), and one small
-  // kernel (head_combine_kernel) forms the candidates -- the DB features and
-  // the f32 logits never reach HBM.  Candidate forwards of the bf16
-  // YOLOv8n-shaped head only (raw forwards keep the decode kernel); the same
-  // candidates as the fixed decode.
-  static const int chain_env = getenv("RV_HEAD_CHAIN") ? atoi(getenv("RV_HEAD_CHAIN")) : -1;
-  bool hchain = (chain_env < 0 ? M->head_chain != 0 : chain_env != 0) && !f8 && fuse_head && !raw_out && cand && v.nc == 80 &&
-                v.reg == 16 && v.c2d == 64 && v.c3d == 80;
-  for (int i = 0; i < 3 && hchain; ++i) {
-    const std::string a = "model.22.cv2." + std::to_string(i), c = "model.22.cv3." + std::to_string(i);
-    hchain = E.head_chain(a + ".1", View{M->DA[i], dcs, 0}, 3 + i, View{M->DB[i], dcs, 0}, a + ".2",
-                          View{M->BX[i], 4, 0}, 2, true) &&
-             E.head_chain(c + ".1", View{M->DA[i], dcs, v.c2d}, 3 + i, View{M->DB[i], dcs, v.c2d},
-                          c + ".2", View{M->SC[i], 2, 0}, 3, true);
-  }
   auto head_level = [&](int i) {
     const std::string a = "model.22.cv2." + std::to_string(i), c = "model.22.cv3." + std::to_string(i);
     E.conv_pair(a + ".0", P[i], c + ".0", P[i], 3 + i, View{M->DA[i], dcs, 0});
-    if (hchain) {
-      E.head_chain(a + ".1", View{M->DA[i], dcs, 0}, 3 + i, View{M->DB[i], dcs, 0}, a + ".2",
-                   View{M->BX[i], 4, 0}, 2, false);
-      E.head_chain(c + ".1", View{M->DA[i], dcs, v.c2d}, 3 + i, View{M->DB[i], dcs, v.c2d}, c + ".2",
-                   View{M->SC[i], 2, 0}, 3, false);
-      return E.status;
-    }
     E.conv_pair(a + ".1", View{M->DA[i], dcs, 0}, c + ".1", View{M->DA[i], dcs, v.c2d}, 3 + i,
                 View{M->DB[i], dcs, 0});
     if (!fuse_head) {
@@ -1373,21 +1287,6 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
       E.status = hip_check(hipStreamWaitEvent(main_s, M->ev_join[i], 0), "head join wait");
   if (E.status) return E.status;
   if (M->prof.on && M->prof.n_fwd < M->prof.cap_fwd) M->prof.n_fwd++;
-  if (hchain) {
-    HeadCombine hc;
-    memset(&hc, 0, sizeof(hc));
-    hc.nlv = 3;
-    for (int i = 0; i < 3; ++i) {
-      hc.bx[i] = (const float*)E.ptr(M->BX[i]);
-      hc.sc[i] = (const float*)E.ptr(M->SC[i]);
-      hc.H[i] = M->map_h[3 + i];
-      hc.W[i] = M->map_w[3 + i];
-      hc.stride[i] = (float)(8 << i);
-      hc.start[i + 1] = hc.start[i] + hc.H[i] * hc.W[i];
-      hc.blk[i + 1] = hc.blk[i] + ceil_div(hc.H[i] * hc.W[i], 64);
-    }
-    return launch_head_combine(hc, B, conf, (Cand*)cand, cand_cap, cand_n, E.s);
-  }
   HeadLevel hl[3];
   memset(hl, 0, sizeof(hl));
   for (int i = 0; i < 3; ++i) {

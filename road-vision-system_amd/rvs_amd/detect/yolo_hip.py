@@ -225,14 +225,6 @@ class YoloEngine:
         for h in self._hs:
             call("rv_yolo_set_option", h, 5, 1 if on else 0)
 
-    def set_head_chain(self, on: bool) -> None:
-        """Candidate forwards run each Detect branch's last 1x1 conv inside
-        its 3x3 conv's launch plus one small combine kernel (True)
-        or through the decode kernel (RV_YOLO_OPT_HEAD_CHAIN; the same
-        candidates; off by default)."""
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 6, 1 if on else 0)
-
     def set_c2f_tap_pairs(self, on: bool) -> None:
         """The fused width-16 C2f chain's 3x3 convs on tap pairs (True,
         default: within 1 bf16 ulp of the per-tap k order) or one k-step per

@@ -69,7 +69,7 @@ class RoadVisionEngine:
                 # a multi-lane engine runs pipelined stages (schedule.PipelinedRun):
                 # its forwards keep the Detect heads on the stage's own stream
                 # instead of two more side streams per handle sharing the 4
-                # hardware queues (r04: +3 % frames/s; RV_HEAD_STREAMS overrides)
+                # hardware queues (r04: +3 % frames/s)
                 self.detector.set_head_streams(False)
         self.max_det = self.detector.max_det if self.detector is not None else \
             int(det_cfg.get("max_det", 100))

@@ -211,10 +211,12 @@ class PipelinedRun:
     device inputs frames[k] (S,H,W,3) u8 and ts[k] (S,) f64.  After run()
     (and a synchronisation), outs[k] = {"record": step k's pinned host
     record, "proc": step k's proc frames}; the records hold what K step()
-    calls would have produced."""
+    calls would have produced.  prep_after_stem: the preprocess of unit u+1
+    is issued behind the stem of unit u's forward (False: before the whole
+    first half)."""
 
     def __init__(self, eng, frames, ts, mode: str = "native", sync: str = "flow",
-                 units: Optional[List[int]] = None):
+                 units: Optional[List[int]] = None, prep_after_stem: bool = True):
         if mode not in ("native", "eager"):
             raise ValueError(f"mode {mode!r}: expected 'native' or 'eager'")
         if sync not in ("stage", "flow"):
@@ -246,33 +248,17 @@ class PipelinedRun:
         self.procs = [torch.empty((eng.S, eng.H, eng.W, 3), dtype=torch.uint8, device=dev)
                       for _ in range(K)]
         self.sm, self.sp, self.sy, self.st = (torch.cuda.Stream(dev) for _ in range(4))
-        import os
-        if os.environ.get("RV_PREP_PRIORITY"):  # A/B probe: the preprocess stream's priority
-            self.sp = torch.cuda.Stream(dev, priority=int(os.environ["RV_PREP_PRIORITY"]))
-        # A/B probe: RV_HIPRI_STREAMS=sy,sm,st creates those stage streams at
-        # high priority (torch: -1), e.g. the later stages ahead of the next
-        # units' preprocess during the pipeline fill
-        for name in filter(None, os.environ.get("RV_HIPRI_STREAMS", "").split(",")):
-            if name not in ("sm", "sp", "sy", "st"):
-                raise ValueError(f"RV_HIPRI_STREAMS: unknown stream {name!r}")
-            setattr(self, name, torch.cuda.Stream(dev, priority=-1))
-        # RV_TRACK_ON_Y2=1: the track stage T(u) runs on the second-half
-        # stream right behind Y2(u) (its only producer), one stream fewer
-        # competing for the process's hardware queues
-        if os.environ.get("RV_TRACK_ON_Y2", "0") != "0":
-            self.st = self.sm
         # Y1(u) runs as forward parts 3 + 4 and the preprocess of unit u+1
         # waits for part 3 (the VALU-bound stem and model.2 chain), so the
         # VALU-bound median pass overlaps the MFMA-bound rest of the forward
         # instead of the stem; Y1 is then issued before P (r04: +1.0 % with
-        # and without the consumer, five A/B pairs; RV_PREP_AFTER_STEM=0 is
+        # and without the consumer, five A/B pairs; prep_after_stem=False is
         # the r03 order)
-        self.prep_after_stem = os.environ.get("RV_PREP_AFTER_STEM", "1") != "0"
+        self.prep_after_stem = bool(prep_after_stem)
         # unit u's NMS runs on the second-half stream right behind its decode
         # (per-slot NMS outputs), not at the head of T(u): at the end of a
         # run it then overlaps the SORT steps of unit u-1 instead of
-        # following them (RV_NMS_ON_Y2=0: the NMS at the head of T(u))
-        self.nms_on_y2 = os.environ.get("RV_NMS_ON_Y2", "1") != "0"
+        # following them
         self._nms_out = {}
         self.sched = None
         self._events = None
@@ -308,18 +294,14 @@ class PipelinedRun:
     def _y2(self, u: int) -> None:
         slots = self.eng.detector.slots
         self.eng.yolo_stage(None, u % slots, u % 2, part=2, batch=self.units[u] * self.eng.S)
-        if self.nms_on_y2:
-            self._nms_out[u] = self.eng.detector.nms(self.units[u] * self.eng.S, u % slots)
+        self._nms_out[u] = self.eng.detector.nms(self.units[u] * self.eng.S, u % slots)
 
     def _track(self, u: int, E: "_Events") -> None:
         """SORT + hand-back of each step of the unit in order, on the NMS
-        output of its slot (run by Y2(u); RV_NMS_ON_Y2=0: here, first); a
-        timing event marks each step's completion."""
+        output of its slot (run by Y2(u)); a timing event marks each step's
+        completion."""
         eng, S, P = self.eng, self.eng.S, self.units[u]
-        if self.nms_on_y2:
-            dets, det_n = self._nms_out.pop(u)
-        else:
-            dets, det_n = eng.detector.nms(S * P, u % eng.detector.slots)
+        dets, det_n = self._nms_out.pop(u)
         for h in range(P):
             k = self.k0[u] + h
             eng.track_handback(dets[h * S:(h + 1) * S], det_n[h * S:(h + 1) * S], self.ts[k],

@@ -117,8 +117,7 @@ def test_results_record_matches_device_outputs(cuda):
     ("eager", "flow", 2, None, "1"), ("eager", "stage", 1, None, "1"),
     ("native", "flow", 4, [1, 2, 4, 1], "1"), ("eager", "flow", 2, [1, 1, 2, 2, 1, 1], "1"),
     ("native", "flow", 2, None, "0"), ("eager", "flow", 4, [4, 2, 2], "0")])
-def test_pipelined_run_matches_sequential_steps(cuda, monkeypatch, mode, sync, pair, units,
-                                                after_stem):
+def test_pipelined_run_matches_sequential_steps(cuda, mode, sync, pair, units, after_stem):
     """bench.py's timed mode (rvs_amd.schedule.PipelinedRun): units of `pair`
     steps software-pipelined over four HIP streams -- preprocess of unit u+1,
     the two forward halves of units u and u-1 on two lanes, NMS + SORT +
@@ -133,7 +132,6 @@ def test_pipelined_run_matches_sequential_steps(cuda, monkeypatch, mode, sync, p
     from rvs_amd.engine import RoadVisionEngine
     from rvs_amd.schedule import PipelinedRun
     from rvs_amd.synth import road_frames
-    monkeypatch.setenv("RV_PREP_AFTER_STEM", after_stem)
     cfg = _cfg()
     S, H, W = 4, 1080, 1920
     K = 8  # a multiple of pair
@@ -153,7 +151,8 @@ def test_pipelined_run_matches_sequential_steps(cuda, monkeypatch, mode, sync, p
     for r in range(2):  # two runs over two windows of K steps
         f0 = 1 + r * K
         run = PipelinedRun(pip, [frames[f0 + k] for k in range(K)],
-                           [ts[f0 + k] for k in range(K)], mode=mode, sync=sync, units=units)
+                           [ts[f0 + k] for k in range(K)], mode=mode, sync=sync, units=units,
+                           prep_after_stem=after_stem != "0")
         if mode == "native":
             assert run.sched.num_nodes() > 0
         run.run()

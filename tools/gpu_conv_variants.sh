@@ -3,7 +3,7 @@
 # variant of VARS (RV_LIB_VARIANT; "default" = librvhip.so), ROUNDS times,
 # with the extra environment ENVS; prints the conv sum and the lines of
 # layers matching PICK.
-#   TAG=x VARS="default nosig" ENVS="RV_HEAD_CHAIN=1" PICK="model.22.cv3.0" bash tools/gpu_conv_variants.sh
+#   TAG=x VARS="default nosig" ENVS="RV_SORT_FUSED=0" PICK="model.22.cv3.0" bash tools/gpu_conv_variants.sh
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${TAG:-cv}
