@@ -124,6 +124,72 @@ int rv_clahe_median_letterbox_fits(int H, int W, int tiles, int k, const int* ge
 int rv_gray_span_u8(const uint8_t* in, int B, int H, int W, int pitch,
                     int* ws, int* span_out, void* stream);
 
+/* PreprocessPipeline.__call__ (src/preprocess/pipeline.py:32-45) of any
+ * chain of the built-in ops, followed by the detector's LetterBox
+ * (src/detect/yolo_ultralytics.py:28-35), as stream-ordered launches only:
+ * no allocation, no host read of device data, no synchronisation.
+ *
+ * The chain is a fixed-size host descriptor read at call time (a launch
+ * schedule copies it by value, like geo).  Per frame:
+ *   !enabled or n_ops == 0                      -> proc = raw
+ *   gate_on and not (double)span < thresh       -> proc = raw
+ *     (span = rv_gray_span_u8's max - min of BGR2GRAY; pipeline.py:24-30,37-40)
+ *   else                                        -> proc = ops applied in order
+ * then lb = LetterBox(proc).  Ops may repeat and come in any order; their
+ * parameters are the normalised ones (clahe_dehaze.py:14-17: tiles =
+ * max(2, tile_grid); median_derain.py:11-13: k odd in [3, 9]). */
+#define RV_CHAIN_CLAHE 0
+#define RV_CHAIN_MEDIAN 1
+#define RV_CHAIN_YCRCB 0
+#define RV_CHAIN_LAB 1
+#define RV_CHAIN_MAX_OPS 4
+typedef struct rv_chain_op {
+  int32_t kind;  /* RV_CHAIN_CLAHE / RV_CHAIN_MEDIAN */
+  int32_t space; /* CLAHE: RV_CHAIN_YCRCB / RV_CHAIN_LAB */
+  int32_t tiles; /* CLAHE: grid, 2..64 */
+  int32_t k;     /* median: 3, 5, 7 or 9 */
+  double clip;   /* CLAHE: clipLimit */
+} rv_chain_op;
+typedef struct rv_chain_desc {
+  int32_t enabled; /* preprocess.enabled */
+  int32_t n_ops;   /* 0..RV_CHAIN_MAX_OPS */
+  int32_t gate_on; /* auto_gate.enable_low_contrast_gate */
+  int32_t reserved;
+  double contrast_thresh; /* auto_gate.contrast_thresh */
+  rv_chain_op ops[RV_CHAIN_MAX_OPS];
+} rv_chain_desc;
+#define RV_CHAIN_DESC_BYTES 120 /* sizeof(rv_chain_desc) */
+
+/* How rv_preprocess_chain_u8 runs a configuration (host only, no GPU):
+ * RV_CHAIN_ROUTE_FUSED: [CLAHE(YCrCb), median 3], gate off, in the fused
+ *   CLAHE + median (+ letterbox) pass: the launches of
+ *   rv_clahe_median_letterbox_u8 (rv_clahe_median_u8 when geo is NULL);
+ * RV_CHAIN_ROUTE_FUSED_GATED: the same chain with the gate on: three small
+ *   gate launches, then the same single pass in which a passed frame's
+ *   blocks copy raw to proc and letterbox raw;
+ * RV_CHAIN_ROUTE_OPS: everything else, op by op (adjacent CLAHE(YCrCb) +
+ *   median fused where rv_clahe_median_fits), ping-pong between `out` and
+ *   one scratch batch, then rv_letterbox_u8's kernel.
+ * geo (nullable: no letterbox wanted) as rv_letterbox_geometry writes it.
+ * RV_EINVAL for a bad descriptor. */
+#define RV_CHAIN_ROUTE_FUSED 0
+#define RV_CHAIN_ROUTE_FUSED_GATED 1
+#define RV_CHAIN_ROUTE_OPS 2
+int rv_preprocess_chain_route(const rv_chain_desc* desc, int H, int W, const int* geo);
+/* Workspace bytes for B frames of H x W with `pitch` bytes per row: the gate's
+ * 2*B ints + B flags, the largest op's LUTs, and one scratch batch
+ * (B*H*pitch) when the chain runs as two or more passes.  0 for a bad
+ * descriptor or shape (and when nothing is needed). */
+size_t rv_preprocess_chain_ws_bytes(const rv_chain_desc* desc, int B, int H, int W, int pitch);
+/* in -> out (proc) and, when lb_out and geo are both given, the letterbox
+ * of proc -> lb_out (B x geo[0] x geo[1] x 3).  in, out and ws may not
+ * alias.  out may be NULL for a disabled or empty chain ("proc is the
+ * input": only the letterbox is produced).  A LAB op needs rv_lab_init() on the device beforehand when the
+ * call must not synchronise (a recorded schedule). */
+int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int pitch,
+                           const rv_chain_desc* desc, void* ws, size_t ws_bytes,
+                           uint8_t* lb_out, const int* geo, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Detect: YOLOUltralytics (src/detect/yolo_ultralytics.py:26-53).           */
 /* ------------------------------------------------------------------------ */
@@ -556,7 +622,8 @@ int rv_capture_close(void* handle);
 #define RV_SCHED_SORT_UPDATE 5            /* rv_sort_update */
 #define RV_SCHED_HANDBACK 6               /* rv_results_handback */
 #define RV_SCHED_UNTRACKED 7              /* rv_untracked_metrics */
-#define RV_SCHED_NUM_OPS 8
+#define RV_SCHED_PREPROCESS_CHAIN 8        /* rv_preprocess_chain_u8 */
+#define RV_SCHED_NUM_OPS 9
 int rv_sched_create(void** handle);
 int rv_sched_destroy(void* handle);
 int rv_sched_add_op(void* handle, int op, const int64_t* iargs, int ni, const double* fargs,

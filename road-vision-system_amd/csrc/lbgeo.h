@@ -90,5 +90,8 @@ inline bool lbgeo_from(const int* geo, int H, int W, LbGeo& g) {
 
 // Fill only the 114 border of B letterboxed images (letterbox.hip).
 int launch_letterbox_pad(uint8_t* out, int B, const LbGeo& g, hipStream_t s);
+// The whole letterbox of B frames (rv_letterbox_u8's kernel; letterbox.hip).
+void launch_letterbox(const uint8_t* in, uint8_t* out, int B, int H, int W, int pitch,
+                      const LbGeo& g, hipStream_t s);
 
 }  // namespace rv

@@ -89,6 +89,12 @@ int launch_letterbox_pad(uint8_t* out, int B, const LbGeo& g, hipStream_t s) {
   return launch_status("letterbox_pad");
 }
 
+void launch_letterbox(const uint8_t* in, uint8_t* out, int B, int H, int W, int pitch,
+                      const LbGeo& g, hipStream_t s) {
+  dim3 grid(ceil_div(g.out_w, 256), g.out_h, B);
+  letterbox_kernel<<<grid, 256, 0, s>>>(in, out, H, W, pitch, g);
+}
+
 }  // namespace rv
 
 using namespace rv;
@@ -120,7 +126,6 @@ extern "C" int rv_letterbox_u8(const uint8_t* in, uint8_t* out, int B, int H, in
   LbGeo g;
   RV_CHECK_ARG(lbgeo_from(geo, H, W, g), "inconsistent letterbox geometry");
   if (B == 0) return RV_OK;
-  dim3 grid(ceil_div(g.out_w, 256), g.out_h, B);
-  letterbox_kernel<<<grid, 256, 0, as_stream(stream)>>>(in, out, H, W, pitch, g);
+  launch_letterbox(in, out, B, H, W, pitch, g, as_stream(stream));
   return launch_status("rv_letterbox_u8");
 }

@@ -276,6 +276,27 @@ static bool clahe_packed_ok(const ClaheGeo& g) {
   return 8 * per_thread <= 65535;
 }
 
+// Gate-aware form (rv_preprocess_chain_u8): flags[b] == 0 marks a frame the
+// low-contrast gate passed through; its LUTs are never read.
+template <int SPACE, bool PACKED>
+__global__ __launch_bounds__(256) void clahe_lut_gate_kernel(const uint8_t* __restrict__ in,
+                                                             uint8_t* __restrict__ lut, int H,
+                                                             int W, int pitch, ClaheGeo g,
+                                                             const int* __restrict__ flags) {
+  if (flags[blockIdx.y] == 0) return;
+  clahe_lut_body<SPACE, PACKED>(in, lut, H, W, pitch, g, blockIdx.x, blockIdx.y, threadIdx.x);
+}
+
+template <int SPACE>
+static void launch_clahe_lut_gate(const uint8_t* in, uint8_t* lut, int B, int H, int W, int pitch,
+                                  const ClaheGeo& g, const int* flags, hipStream_t s) {
+  const dim3 grid(g.tiles * g.tiles, B);
+  if (clahe_packed_ok(g))
+    clahe_lut_gate_kernel<SPACE, true><<<grid, 256, 0, s>>>(in, lut, H, W, pitch, g, flags);
+  else
+    clahe_lut_gate_kernel<SPACE, false><<<grid, 256, 0, s>>>(in, lut, H, W, pitch, g, flags);
+}
+
 template <int SPACE>
 static void launch_clahe_lut(const uint8_t* in, uint8_t* lut, int B, int H, int W, int pitch,
                              const ClaheGeo& g, hipStream_t s) {
@@ -319,8 +340,10 @@ template <int SPACE>
 __global__ __launch_bounds__(256) void clahe_apply_kernel(const uint8_t* __restrict__ in,
                                                           uint8_t* __restrict__ out,
                                                           const uint8_t* __restrict__ lut, int H,
-                                                          int W, int pitch, ClaheGeo g) {
+                                                          int W, int pitch, ClaheGeo g,
+                                                          const int* __restrict__ flags) {
   const int b = blockIdx.z;
+  if (flags != nullptr && flags[b] == 0) return;  // a frame the gate passed through
   const uint8_t* fin = in + (size_t)b * H * pitch;
   uint8_t* fout = out + (size_t)b * H * pitch;
   const uint8_t* flut = lut + (size_t)b * g.tiles * g.tiles * 256;
@@ -434,9 +457,11 @@ template <int K, bool CLAHE>
 __global__ __launch_bounds__(256) void median_tile_kernel(const uint8_t* __restrict__ in,
                                                           uint8_t* __restrict__ out,
                                                           const uint8_t* __restrict__ lut, int H,
-                                                          int W, int pitch, ClaheGeo g) {
+                                                          int W, int pitch, ClaheGeo g,
+                                                          const int* __restrict__ flags) {
   using T = MedTile<K>;
   constexpr int R = T::R;
+  if (flags != nullptr && flags[blockIdx.z] == 0) return;  // a frame the gate passed through
   __shared__ __attribute__((aligned(16))) uint8_t raw[T::TH * T::RAWP];
   __shared__ __attribute__((aligned(16))) uint8_t proc[T::TH * T::PROC + 16];
   __shared__ __attribute__((aligned(16))) uint8_t lwin[CLAHE ? kLutWinMax * 256 : 16];
@@ -690,12 +715,16 @@ __device__ __forceinline__ void clahe_ycc(int bb, int gg, int rr, const uint8_t*
   tr = dcr * (22987 * 4) + 8192 * 4;
 }
 
-// One 128 x 32 block (b, x0, y0).
-template <bool CLAHE, bool LB>
+// One 128 x 32 block (b, x0, y0).  GATE (med3_gate_kernel only): `pass`
+// (block-uniform) marks a frame the low-contrast gate passed through: its
+// raw tile goes to `out` untouched and its letterbox pixels come from raw.
+// Without GATE `raw` below is a compile-time false and nothing changes.
+template <bool CLAHE, bool LB, bool GATE = false>
 __device__ __forceinline__ void med3_body(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
                                           const uint8_t* __restrict__ lut, int H, int W, int pitch,
                                           int vec, const ClaheGeo& g, const LbFuse& lb, int b,
-                                          int x0, int y0, int tid) {
+                                          int x0, int y0, int tid, bool pass = false) {
+  const bool raw = GATE && pass;
   __shared__ __attribute__((aligned(16))) uint8_t tile[kM3TH * kM3Stride];  // halo, then medians
   extern __shared__ __attribute__((aligned(16))) uint32_t cells[];  // CLAHE cells (host-sized)
 
@@ -763,7 +792,7 @@ __device__ __forceinline__ void med3_body(const uint8_t* __restrict__ in, uint8_
     const int ncy = clahe_cell_index(gy_hi, g.inv_th) - cy0 + 1;
     const uint32_t* flut = (const uint32_t*)(lut + (size_t)b * g.tiles * g.tiles * 256);
     const int lane = tid & 63;
-    for (int c = tid >> 6; c < ncx * ncy; c += 4) {
+    for (int c = tid >> 6; c < (raw ? 0 : ncx * ncy); c += 4) {
       const int cy = c / ncx, cx = c - (c / ncx) * ncx;
       const int iy = cy0 + cy, ix = cx0 + cx;
       const int r1 = max(iy, 0), r2 = min(iy + 1, g.tiles - 1);
@@ -799,7 +828,7 @@ __device__ __forceinline__ void med3_body(const uint8_t* __restrict__ in, uint8_
     const int hr = rs + 8 * it;
     if (hr >= kM3TH) break;
     uint32_t* dst = (uint32_t*)(tile + hr * kM3Stride + (gc + 1) * 12);
-    if constexpr (CLAHE) {
+    if (CLAHE && !raw) {
       f32x2 yw;
       const uint32_t* crow = clahe_row(y0 - 1 + hr, H, g.inv_th, cy0, ncx, cells, yw);
       uint32_t y2[4];
@@ -823,7 +852,7 @@ __device__ __forceinline__ void med3_body(const uint8_t* __restrict__ in, uint8_
   }
   if (side) {
     uint8_t* dst = tile + s_hr * kM3Stride + ((sk & 1) ? 12 * (kM3W / 4 + 1) : 9);
-    if constexpr (CLAHE) {
+    if (CLAHE && !raw) {
       f32x2 sxw, yw;
       int sxoff;
       clahe_x(s_px, g.inv_tw, cx0, sxw, sxoff);
@@ -861,29 +890,35 @@ __device__ __forceinline__ void med3_body(const uint8_t* __restrict__ in, uint8_
 #pragma unroll
   for (int o = 0; o < 4; ++o, orow += pitch) {
     const int y = y0 + ry + o;
-    uint32_t v12[12];  // medians, byte order b0 g0 r0 b1 ...
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      uint32_t lo[6], mi[6], hi[6];
-#pragma unroll
-      for (int jj = 0; jj < 6; ++jj) {
-        const uint32_t a = RV_B(o, 1 + 3 * jj + c), bq = RV_B(o + 1, 1 + 3 * jj + c),
-                       e = RV_B(o + 2, 1 + 3 * jj + c);
-        lo[jj] = min(min(a, bq), e);
-        hi[jj] = max(max(a, bq), e);
-        mi[jj] = med3_u32(a, bq, e);
-      }
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const uint32_t l = max(max(lo[p], lo[p + 1]), lo[p + 2]);
-        const uint32_t m = med3_u32(mi[p], mi[p + 1], mi[p + 2]);
-        const uint32_t h = min(min(hi[p], hi[p + 1]), hi[p + 2]);
-        v12[3 * p + c] = med3_u32(l, m, h);
-      }
-    }
     uint32_t res[3];
+    if (raw) {
+      // window bytes 4..15 of the centre row are the 4 output pixels themselves
 #pragma unroll
-    for (int w = 0; w < 3; ++w) res[w] = pack_u8x4(v12[4 * w], v12[4 * w + 1], v12[4 * w + 2], v12[4 * w + 3]);
+      for (int w = 0; w < 3; ++w) res[w] = rw[o + 1][1 + w];
+    } else {
+      uint32_t v12[12];  // medians, byte order b0 g0 r0 b1 ...
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        uint32_t lo[6], mi[6], hi[6];
+#pragma unroll
+        for (int jj = 0; jj < 6; ++jj) {
+          const uint32_t a = RV_B(o, 1 + 3 * jj + c), bq = RV_B(o + 1, 1 + 3 * jj + c),
+                         e = RV_B(o + 2, 1 + 3 * jj + c);
+          lo[jj] = min(min(a, bq), e);
+          hi[jj] = max(max(a, bq), e);
+          mi[jj] = med3_u32(a, bq, e);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const uint32_t l = max(max(lo[p], lo[p + 1]), lo[p + 2]);
+          const uint32_t m = med3_u32(mi[p], mi[p + 1], mi[p + 2]);
+          const uint32_t h = min(min(hi[p], hi[p + 1]), hi[p + 2]);
+          v12[3 * p + c] = med3_u32(l, m, h);
+        }
+      }
+#pragma unroll
+      for (int w = 0; w < 3; ++w) res[w] = pack_u8x4(v12[4 * w], v12[4 * w + 1], v12[4 * w + 2], v12[4 * w + 3]);
+    }
     if constexpr (LB) {
       uint32_t* od = (uint32_t*)(tile + (ry + o) * kM3Stride + rx * 3);
       od[0] = res[0];
@@ -978,6 +1013,30 @@ __global__ __launch_bounds__(256) void med3_kernel(const uint8_t* __restrict__ i
                               (f - (f / ntx) * ntx) * kM3W, (f / ntx) * kM3H, threadIdx.x);
 }
 
+// The gate-aware launch (rv_preprocess_chain_u8): same tile order; flags[b]
+// == 0 marks a frame the gate passed through.  Its blocks either return at
+// once (pass_copy == 0: the caller copies raw into proc) or copy their raw
+// tile to `out` and letterbox it (pass_copy != 0), beside the blocks of the
+// low-contrast frames doing the full work in the same launch.
+template <bool CLAHE, bool LB>
+__global__ __launch_bounds__(256) void med3_gate_kernel(const uint8_t* __restrict__ in,
+                                                        uint8_t* __restrict__ out,
+                                                        const uint8_t* __restrict__ lut, int H,
+                                                        int W, int pitch, int vec, ClaheGeo g,
+                                                        LbFuse lb, const int* __restrict__ flags,
+                                                        int pass_copy) {
+  const int ntx = (W + kM3W - 1) / kM3W, nty = (H + kM3H - 1) / kM3H;
+  const int n = gridDim.x, L = blockIdx.x;
+  const int q = n >> 3, r = n & 7, xcd = L & 7, slot = L >> 3;
+  const int t = xcd < r ? xcd * (q + 1) + slot : r * (q + 1) + (xcd - r) * q + slot;
+  const int b = t / (ntx * nty);
+  const int f = t - b * (ntx * nty);
+  const bool pass = flags[b] == 0;
+  if (pass && !pass_copy) return;
+  med3_body<CLAHE, LB, true>(in, out, lut, H, W, pitch, vec, g, lb, b,
+                             (f - (f / ntx) * ntx) * kM3W, (f / ntx) * kM3H, threadIdx.x, pass);
+}
+
 static size_t lut_bytes(int B, int tiles) { return (size_t)B * tiles * tiles * 256; }
 
 // Host checks for med3_kernel.
@@ -1021,27 +1080,67 @@ static void launch_med3(const uint8_t* in, uint8_t* out, const uint8_t* lut, int
   med3_kernel<CLAHE, LB><<<grid, 256, cell_bytes, s>>>(in, out, lut, H, W, pitch, vec, g, lb);
 }
 
-// Gray span for the low-contrast gate (pipeline.py:24-30).
+template <bool CLAHE, bool LB>
+static void launch_med3_gate(const uint8_t* in, uint8_t* out, const uint8_t* lut, int B, int H,
+                             int W, int pitch, const ClaheGeo& g, const LbFuse& lb,
+                             const int* flags, int pass_copy, hipStream_t s) {
+  const int vec = (pitch % 4 == 0) && (((uintptr_t)in) % 4 == 0) && (((uintptr_t)out) % 4 == 0);
+  const dim3 grid(ceil_div(W, kM3W) * ceil_div(H, kM3H) * B);
+  const size_t cell_bytes = CLAHE ? (size_t)med3_cells(g) * 1024 : 0;
+  med3_gate_kernel<CLAHE, LB><<<grid, 256, cell_bytes, s>>>(in, out, lut, H, W, pitch, vec, g, lb,
+                                                            flags, pass_copy);
+}
+
+// Gray span for the low-contrast gate (pipeline.py:24-30).  A thread takes
+// 4-pixel groups (12 bytes): three dword loads when `vec` (pitch and base
+// 4-byte aligned) and the group lies inside the row, else its pixels one by
+// one (the ragged right edge, unaligned frames).
 __global__ __launch_bounds__(256) void gray_span_kernel(const uint8_t* __restrict__ in, int H,
-                                                        int W, int pitch, int* __restrict__ mn_mx) {
+                                                        int W, int pitch, int vec,
+                                                        int* __restrict__ mn_mx) {
   const int b = blockIdx.y;
   const uint8_t* frame = in + (size_t)b * H * pitch;
   int mn = 255, mx = 0;
-  const int total = H * W;
+  const int groups = (W + 3) >> 2;
+  const int total = H * groups;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int y = i / W, x = i - (i / W) * W;
-    const uint8_t* p = frame + (size_t)y * pitch + (size_t)x * 3;
-    const int v = bgr_to_y(p[0], p[1], p[2]);
-    mn = min(mn, v);
-    mx = max(mx, v);
+    const int y = i / groups, x = (i - y * groups) * 4;
+    const uint8_t* p = frame + (size_t)y * pitch + x * 3;
+    if (vec && x + 3 < W) {
+      const uint32_t w0 = ((const uint32_t*)p)[0], w1 = ((const uint32_t*)p)[1],
+                     w2 = ((const uint32_t*)p)[2];
+      // bytes little-endian: w0 = b0 g0 r0 b1 | w1 = g1 r1 b2 g2 | w2 = r2 b3 g3 r3
+      const int v0 = bgr_to_y(w0 & 255, (w0 >> 8) & 255, (w0 >> 16) & 255);
+      const int v1 = bgr_to_y(w0 >> 24, w1 & 255, (w1 >> 8) & 255);
+      const int v2 = bgr_to_y((w1 >> 16) & 255, w1 >> 24, w2 & 255);
+      const int v3 = bgr_to_y((w2 >> 8) & 255, (w2 >> 16) & 255, w2 >> 24);
+      mn = min(mn, min(min(v0, v1), min(v2, v3)));
+      mx = max(mx, max(max(v0, v1), max(v2, v3)));
+    } else {
+      const int n = min(4, W - x);
+      for (int j = 0; j < n; ++j) {
+        const int v = bgr_to_y(p[3 * j], p[3 * j + 1], p[3 * j + 2]);
+        mn = min(mn, v);
+        mx = max(mx, v);
+      }
+    }
   }
   for (int off = 32; off > 0; off >>= 1) {
     mn = min(mn, __shfl_xor(mn, off));
     mx = max(mx, __shfl_xor(mx, off));
   }
+  // one atomic pair per block: the 2 B words share a few cache lines, and
+  // the atomics of every wave of 256 blocks per frame serialised on them
+  // (0.45 ms per 32 x 1080p, ten times the read)
+  __shared__ int smn[4], smx[4];
   if ((threadIdx.x & 63) == 0) {
-    atomicMin(&mn_mx[2 * b], mn);
-    atomicMax(&mn_mx[2 * b + 1], mx);
+    smn[threadIdx.x >> 6] = mn;
+    smx[threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicMin(&mn_mx[2 * b], min(min(smn[0], smn[1]), min(smn[2], smn[3])));
+    atomicMax(&mn_mx[2 * b + 1], max(max(smx[0], smx[1]), max(smx[2], smx[3])));
   }
 }
 __global__ void gray_span_init(int* mn_mx, int B) {
@@ -1056,6 +1155,50 @@ __global__ void gray_span_finish(const int* mn_mx, int* span, int B) {
   if (i < B) span[i] = mn_mx[2 * i + 1] - mn_mx[2 * i];
 }
 
+// The gate of rv_preprocess_chain_u8: flags[b] = 1 for a low-contrast frame
+// (pipeline.py:28-29: span < contrast_thresh, compared in double as Python
+// compares int < float), 0 for a frame that passes through unchanged.
+__global__ void gray_span_gate(const int* mn_mx, int* flags, int B, double thresh) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B) flags[i] = (double)(mn_mx[2 * i + 1] - mn_mx[2 * i]) < thresh ? 1 : 0;
+}
+
+// in -> out for every frame (flags == nullptr) or for the frames the gate
+// passed through (flags[b] == 0).  16 bytes per thread, rows by blockIdx.y.
+__global__ __launch_bounds__(256) void copy_frames_kernel(const uint8_t* __restrict__ in,
+                                                          uint8_t* __restrict__ out, int H,
+                                                          int rowbytes, int pitch, int vec,
+                                                          const int* __restrict__ flags) {
+  const int b = blockIdx.z;
+  if (flags != nullptr && flags[b] != 0) return;
+  const int i = (blockIdx.x * 256 + threadIdx.x) * 16;
+  if (i >= rowbytes) return;
+  for (int y = blockIdx.y; y < H; y += gridDim.y) {
+    const size_t off = ((size_t)b * H + y) * pitch + i;
+    if (vec && i + 16 <= rowbytes) {
+      *(uint4*)(out + off) = *(const uint4*)(in + off);
+    } else {
+      const int n = min(16, rowbytes - i);
+      for (int j = 0; j < n; ++j) out[off + j] = in[off + j];
+    }
+  }
+}
+
+static void launch_copy_frames(const uint8_t* in, uint8_t* out, int B, int H, int W, int pitch,
+                               const int* flags, hipStream_t s) {
+  const int vec = (pitch % 16 == 0) && (((uintptr_t)in) % 16 == 0) && (((uintptr_t)out) % 16 == 0);
+  const dim3 grid(ceil_div(W * 3, 256 * 16), min(H, 65535), B);
+  copy_frames_kernel<<<grid, 256, 0, s>>>(in, out, H, W * 3, pitch, vec, flags);
+}
+
+static void launch_gray_span(const uint8_t* in, int B, int H, int W, int pitch, int* mn_mx,
+                             hipStream_t s) {
+  const int vec = (pitch % 4 == 0) && (((uintptr_t)in) % 4 == 0);
+  const int blocks = min(64, ceil_div(H * ((W + 3) / 4), 256));
+  gray_span_init<<<ceil_div(B, 256), 256, 0, s>>>(mn_mx, B);
+  gray_span_kernel<<<dim3(blocks, B), 256, 0, s>>>(in, H, W, pitch, vec, mn_mx);
+}
+
 static bool lut_window_fits(const ClaheGeo& g, int K) {
   const int R = K / 2;
   // worst-case tile columns/rows touched by one (kBW+2R) x (kBH+2R) halo tile
@@ -1066,19 +1209,21 @@ static bool lut_window_fits(const ClaheGeo& g, int K) {
 
 template <int K, bool CLAHE>
 static void launch_median(const uint8_t* in, uint8_t* out, const uint8_t* lut, int B, int H,
-                          int W, int pitch, const ClaheGeo& g, hipStream_t s) {
+                          int W, int pitch, const ClaheGeo& g, hipStream_t s,
+                          const int* flags = nullptr) {
   dim3 grid(ceil_div(W, kBW), ceil_div(H, kBH), B);
-  median_tile_kernel<K, CLAHE><<<grid, 256, 0, s>>>(in, out, lut, H, W, pitch, g);
+  median_tile_kernel<K, CLAHE><<<grid, 256, 0, s>>>(in, out, lut, H, W, pitch, g, flags);
 }
 
 template <bool CLAHE>
 static void dispatch_median(int k, const uint8_t* in, uint8_t* out, const uint8_t* lut, int B,
-                            int H, int W, int pitch, const ClaheGeo& g, hipStream_t s) {
+                            int H, int W, int pitch, const ClaheGeo& g, hipStream_t s,
+                            const int* flags = nullptr) {
   switch (k) {
-    case 3: launch_median<3, CLAHE>(in, out, lut, B, H, W, pitch, g, s); break;
-    case 5: launch_median<5, CLAHE>(in, out, lut, B, H, W, pitch, g, s); break;
-    case 7: launch_median<7, CLAHE>(in, out, lut, B, H, W, pitch, g, s); break;
-    default: launch_median<9, CLAHE>(in, out, lut, B, H, W, pitch, g, s); break;
+    case 3: launch_median<3, CLAHE>(in, out, lut, B, H, W, pitch, g, s, flags); break;
+    case 5: launch_median<5, CLAHE>(in, out, lut, B, H, W, pitch, g, s, flags); break;
+    case 7: launch_median<7, CLAHE>(in, out, lut, B, H, W, pitch, g, s, flags); break;
+    default: launch_median<9, CLAHE>(in, out, lut, B, H, W, pitch, g, s, flags); break;
   }
 }
 
@@ -1112,7 +1257,7 @@ extern "C" int rv_clahe_ycrcb_u8(const uint8_t* in, uint8_t* out, int B, int H, 
   uint8_t* lut = (uint8_t*)ws;
   launch_clahe_lut<kYCrCb>(in, lut, B, H, W, pitch, g, s);
   clahe_apply_kernel<kYCrCb><<<dim3(1, ceil_div(H, kApplyRows), B), 256, 0, s>>>(in, out, lut, H, W,
-                                                                          pitch, g);
+                                                                          pitch, g, nullptr);
   return launch_status("rv_clahe_ycrcb_u8");
 }
 
@@ -1176,7 +1321,7 @@ extern "C" int rv_clahe_lab_u8(const uint8_t* in, uint8_t* out, int B, int H, in
   uint8_t* lut = (uint8_t*)ws;
   launch_clahe_lut<kLab>(in, lut, B, H, W, pitch, g, s);
   clahe_apply_kernel<kLab><<<dim3(1, ceil_div(H, kApplyRows), B), 256, 0, s>>>(in, out, lut, H,
-                                                                              W, pitch, g);
+                                                                              W, pitch, g, nullptr);
   return launch_status("rv_clahe_lab_u8");
 }
 
@@ -1253,9 +1398,246 @@ extern "C" int rv_gray_span_u8(const uint8_t* in, int B, int H, int W, int pitch
   RV_CHECK_ARG(B >= 0 && H > 0 && W > 0 && pitch >= 3 * W, "bad frame shape");
   if (B == 0) return RV_OK;
   hipStream_t s = as_stream(stream);
-  gray_span_init<<<ceil_div(B, 256), 256, 0, s>>>(ws, B);
-  const int blocks = min(256, ceil_div(H * W, 256));
-  gray_span_kernel<<<dim3(blocks, B), 256, 0, s>>>(in, H, W, pitch, ws);
+  launch_gray_span(in, B, H, W, pitch, ws, s);
   gray_span_finish<<<ceil_div(B, 256), 256, 0, s>>>(ws, span_out, B);
   return launch_status("rv_gray_span_u8");
+}
+
+// ---------------------------------------------------------------------------
+// rv_preprocess_chain_u8: any chain of the built-in ops + the low-contrast
+// gate + the detector's LetterBox as stream-ordered launches (rvhip.h).
+// ---------------------------------------------------------------------------
+static_assert(sizeof(rv_chain_desc) == RV_CHAIN_DESC_BYTES, "rv_chain_desc layout");
+
+namespace {
+
+enum PassKind { kPassClahe = 0, kPassMedian = 1, kPassClaheMedian = 2 };
+
+struct ChainPass {
+  int kind, space, tiles, k;
+  double clip;
+};
+
+// How a descriptor runs on an H x W frame: the passes (adjacent CLAHE(YCrCb)
+// + median fused where rv_clahe_median_u8 would), the route and the
+// workspace layout [gate ints | LUTs | scratch batch].
+struct ChainPlan {
+  bool identity;  // disabled or empty chain: proc = raw
+  bool gate, lab;
+  int n;
+  ChainPass pass[RV_CHAIN_MAX_OPS];
+  int route;
+  int lut_tiles;  // largest CLAHE grid (0: no CLAHE)
+};
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int check_desc(const rv_chain_desc* d) {
+  RV_CHECK_ARG(d != nullptr, "null chain descriptor");
+  RV_CHECK_ARG((d->enabled == 0 || d->enabled == 1) && (d->gate_on == 0 || d->gate_on == 1),
+               "chain descriptor: enabled=%d gate_on=%d must be 0 or 1", d->enabled, d->gate_on);
+  RV_CHECK_ARG(d->n_ops >= 0 && d->n_ops <= RV_CHAIN_MAX_OPS, "chain descriptor: n_ops=%d not in 0..%d",
+               d->n_ops, RV_CHAIN_MAX_OPS);
+  RV_CHECK_ARG(d->contrast_thresh == d->contrast_thresh, "chain descriptor: contrast_thresh is NaN");
+  for (int i = 0; i < d->n_ops; ++i) {
+    const rv_chain_op& o = d->ops[i];
+    if (o.kind == RV_CHAIN_CLAHE) {
+      RV_CHECK_ARG(o.space == RV_CHAIN_YCRCB || o.space == RV_CHAIN_LAB,
+                   "chain op %d: CLAHE space %d", i, o.space);
+      RV_CHECK_ARG(o.tiles >= 2 && o.tiles <= 64, "chain op %d: CLAHE tiles %d not in 2..64", i,
+                   o.tiles);
+      RV_CHECK_ARG(o.clip == o.clip, "chain op %d: CLAHE clip is NaN", i);
+    } else if (o.kind == RV_CHAIN_MEDIAN) {
+      RV_CHECK_ARG(o.k == 3 || o.k == 5 || o.k == 7 || o.k == 9,
+                   "chain op %d: median k=%d must be 3,5,7,9", i, o.k);
+    } else {
+      RV_CHECK_ARG(false, "chain op %d: unknown kind %d", i, o.kind);
+    }
+  }
+  return RV_OK;
+}
+
+bool clahe_median_fuses(int H, int W, int tiles, int k) {
+  const ClaheGeo g = make_geo(H, W, tiles, 0.0);
+  return (k == 3 && med3_cells_fit(g, H, W)) || lut_window_fits(g, k);
+}
+
+// G: the letterbox wanted (nullptr: none).  The descriptor is already checked.
+void make_plan(const rv_chain_desc& d, int H, int W, const LbGeo* G, ChainPlan& p) {
+  p.identity = !d.enabled || d.n_ops == 0;
+  p.gate = !p.identity && d.gate_on;
+  p.lab = false;
+  p.n = 0;
+  p.lut_tiles = 0;
+  p.route = RV_CHAIN_ROUTE_OPS;
+  if (p.identity) return;
+  for (int i = 0; i < d.n_ops;) {
+    const rv_chain_op& o = d.ops[i];
+    ChainPass& q = p.pass[p.n++];
+    q = ChainPass{o.kind == RV_CHAIN_CLAHE ? kPassClahe : kPassMedian, o.space, o.tiles, o.k, o.clip};
+    if (o.kind == RV_CHAIN_CLAHE) {
+      p.lut_tiles = max(p.lut_tiles, o.tiles);
+      p.lab = p.lab || o.space == RV_CHAIN_LAB;
+      if (o.space == RV_CHAIN_YCRCB && i + 1 < d.n_ops && d.ops[i + 1].kind == RV_CHAIN_MEDIAN &&
+          clahe_median_fuses(H, W, o.tiles, d.ops[i + 1].k)) {
+        q.kind = kPassClaheMedian;
+        q.k = d.ops[i + 1].k;
+        i += 2;
+        continue;
+      }
+    }
+    ++i;
+  }
+  // the single 128 x 32 pass of the default chain (+ the letterbox from its tile)
+  if (p.n == 1 && p.pass[0].kind == kPassClaheMedian && p.pass[0].k == 3 &&
+      med3_cells_fit(make_geo(H, W, p.pass[0].tiles, 0.0), H, W) &&
+      (G == nullptr || med3_lb_fits(*G, H, W)))
+    p.route = p.gate ? RV_CHAIN_ROUTE_FUSED_GATED : RV_CHAIN_ROUTE_FUSED;
+}
+
+struct ChainWs {
+  size_t gate, lut, scratch;  // byte sizes, in this order
+  size_t total() const { return gate + lut + scratch; }
+};
+
+ChainWs plan_ws(const ChainPlan& p, int B, int H, int pitch) {
+  ChainWs w;
+  w.gate = p.gate ? align256((size_t)3 * B * sizeof(int)) : 0;
+  w.lut = p.lut_tiles ? align256(lut_bytes(B, p.lut_tiles)) : 0;
+  w.scratch = p.n >= 2 ? align256((size_t)B * H * pitch) : 0;
+  return w;
+}
+
+// One pass src -> dst (flags: nullptr, or the gate's per-frame flags: frames
+// it passed through are skipped).
+void launch_pass(const ChainPass& q, const uint8_t* src, uint8_t* dst, uint8_t* lut, int B, int H,
+                 int W, int pitch, const int* flags, hipStream_t s) {
+  if (q.kind == kPassMedian) {
+    const ClaheGeo g{};
+    if (q.k != 3)
+      dispatch_median<false>(q.k, src, dst, nullptr, B, H, W, pitch, g, s, flags);
+    else if (flags)
+      launch_med3_gate<false, false>(src, dst, nullptr, B, H, W, pitch, g, LbFuse{}, flags, 0, s);
+    else
+      launch_med3<false, false>(src, dst, nullptr, B, H, W, pitch, g, LbFuse{}, s);
+    return;
+  }
+  const ClaheGeo g = make_geo(H, W, q.tiles, q.clip);
+  if (q.space == RV_CHAIN_LAB) {
+    if (flags) launch_clahe_lut_gate<kLab>(src, lut, B, H, W, pitch, g, flags, s);
+    else launch_clahe_lut<kLab>(src, lut, B, H, W, pitch, g, s);
+    clahe_apply_kernel<kLab><<<dim3(1, ceil_div(H, kApplyRows), B), 256, 0, s>>>(src, dst, lut, H, W,
+                                                                              pitch, g, flags);
+    return;
+  }
+  if (flags) launch_clahe_lut_gate<kYCrCb>(src, lut, B, H, W, pitch, g, flags, s);
+  else launch_clahe_lut<kYCrCb>(src, lut, B, H, W, pitch, g, s);
+  if (q.kind == kPassClahe) {
+    clahe_apply_kernel<kYCrCb><<<dim3(1, ceil_div(H, kApplyRows), B), 256, 0, s>>>(src, dst, lut, H,
+                                                                                W, pitch, g, flags);
+  } else if (q.k == 3 && med3_cells_fit(g, H, W)) {
+    if (flags) launch_med3_gate<true, false>(src, dst, lut, B, H, W, pitch, g, LbFuse{}, flags, 0, s);
+    else launch_med3<true, false>(src, dst, lut, B, H, W, pitch, g, LbFuse{}, s);
+  } else {
+    dispatch_median<true>(q.k, src, dst, lut, B, H, W, pitch, g, s, flags);
+  }
+}
+
+}  // namespace
+
+extern "C" int rv_preprocess_chain_route(const rv_chain_desc* desc, int H, int W, const int* geo) {
+  int st = check_desc(desc);
+  if (st) return st;
+  RV_CHECK_ARG(H > 0 && W > 0, "bad frame shape H=%d W=%d", H, W);
+  LbGeo G;
+  if (geo != nullptr) RV_CHECK_ARG(lbgeo_from(geo, H, W, G), "inconsistent letterbox geometry");
+  ChainPlan p;
+  make_plan(*desc, H, W, geo ? &G : nullptr, p);
+  return p.route;
+}
+
+extern "C" size_t rv_preprocess_chain_ws_bytes(const rv_chain_desc* desc, int B, int H, int W,
+                                               int pitch) {
+  if (check_desc(desc) != RV_OK || B <= 0 || H <= 0 || W <= 0 || pitch < 3 * W) return 0;
+  ChainPlan p;
+  make_plan(*desc, H, W, nullptr, p);  // the layout does not depend on the letterbox
+  return plan_ws(p, B, H, pitch).total();
+}
+
+extern "C" int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, int H, int W,
+                                      int pitch, const rv_chain_desc* desc, void* ws,
+                                      size_t ws_bytes, uint8_t* lb_out, const int* geo,
+                                      void* stream) {
+  int st = check_desc(desc);
+  if (st) return st;
+  // out == nullptr: "proc is the input", for a disabled or empty chain only
+  const bool no_out = out == nullptr && (!desc->enabled || desc->n_ops == 0);
+  st = check_frames(in, no_out ? (const void*)lb_out : (const void*)out, B, H, W, pitch);
+  if (st) return st;
+  RV_CHECK_ARG((lb_out != nullptr) == (geo != nullptr),
+               "lb_out and geo must be given together (lb_out %s, geo %s)",
+               lb_out ? "set" : "null", geo ? "set" : "null");
+  LbFuse lb{};
+  if (geo != nullptr) RV_CHECK_ARG(lbgeo_from(geo, H, W, lb.g), "inconsistent letterbox geometry");
+  ChainPlan p;
+  make_plan(*desc, H, W, geo ? &lb.g : nullptr, p);
+  const ChainWs w = plan_ws(p, B, H, pitch);
+  RV_CHECK_ARG(w.total() == 0 || (ws != nullptr && ws_bytes >= w.total()),
+               "workspace too small: %zu bytes, rv_preprocess_chain_ws_bytes says %zu", ws_bytes,
+               w.total());
+  RV_CHECK_ARG(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
+  if (w.total()) {
+    const uint8_t* w0 = (const uint8_t*)ws;
+    const size_t fb = (size_t)B * H * pitch;
+    RV_CHECK_ARG((w0 + w.total() <= in || in + fb <= w0) &&
+                     (out == nullptr || w0 + w.total() <= out || out + fb <= w0),
+                 "the workspace overlaps the frames");
+  }
+  if (B == 0) return RV_OK;
+  if (p.lab) {
+    st = ensure_lab_tables();
+    if (st) return st;
+  }
+  hipStream_t s = as_stream(stream);
+  int* gate = (int*)ws;  // mn_mx[2 B], then flags[B]
+  const int* flags = p.gate ? gate + 2 * B : nullptr;
+  uint8_t* lut = (uint8_t*)ws + w.gate;
+  uint8_t* scratch = (uint8_t*)ws + w.gate + w.lut;
+  if (p.gate) {
+    launch_gray_span(in, B, H, W, pitch, gate, s);
+    gray_span_gate<<<ceil_div(B, 256), 256, 0, s>>>(gate, gate + 2 * B, B, desc->contrast_thresh);
+  }
+  if (p.route != RV_CHAIN_ROUTE_OPS) {
+    const ClaheGeo g = make_geo(H, W, p.pass[0].tiles, p.pass[0].clip);
+    if (lb_out != nullptr) {
+      lb.out = lb_out;
+      lb.copy = lb_is_copy(lb.g, H, W) ? 1 : 0;
+      st = launch_letterbox_pad(lb_out, B, lb.g, s);
+      if (st) return st;
+    }
+    if (!p.gate) {
+      launch_clahe_lut<kYCrCb>(in, lut, B, H, W, pitch, g, s);
+      if (lb_out != nullptr) launch_med3<true, true>(in, out, lut, B, H, W, pitch, g, lb, s);
+      else launch_med3<true, false>(in, out, lut, B, H, W, pitch, g, lb, s);
+    } else {
+      launch_clahe_lut_gate<kYCrCb>(in, lut, B, H, W, pitch, g, flags, s);
+      if (lb_out != nullptr) launch_med3_gate<true, true>(in, out, lut, B, H, W, pitch, g, lb, flags, 1, s);
+      else launch_med3_gate<true, false>(in, out, lut, B, H, W, pitch, g, lb, flags, 1, s);
+    }
+    return launch_status("rv_preprocess_chain_u8");
+  }
+  if (p.identity) {
+    if (out != nullptr) launch_copy_frames(in, out, B, H, W, pitch, nullptr, s);
+  } else {
+    // the last pass writes `out`; the ones before alternate with the scratch batch
+    const uint8_t* src = in;
+    for (int i = 0; i < p.n; ++i) {
+      uint8_t* dst = ((p.n - 1 - i) & 1) ? scratch : out;
+      launch_pass(p.pass[i], src, dst, lut, B, H, W, pitch, flags, s);
+      src = dst;
+    }
+    if (p.gate) launch_copy_frames(in, out, B, H, W, pitch, flags, s);
+  }
+  if (lb_out != nullptr) launch_letterbox(out ? out : in, lb_out, B, H, W, pitch, lb.g, s);
+  return launch_status("rv_preprocess_chain_u8");
 }

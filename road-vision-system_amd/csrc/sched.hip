@@ -82,6 +82,7 @@ const OpSpec kSpecs[RV_SCHED_NUM_OPS] = {
     /* RV_SCHED_SORT_UPDATE */ {16, 0},
     /* RV_SCHED_HANDBACK */ {10, 0},
     /* RV_SCHED_UNTRACKED */ {9, 1},
+    /* RV_SCHED_PREPROCESS_CHAIN */ {11, 0},
 };
 
 int issue_op(const Node& n) {
@@ -137,6 +138,13 @@ int issue_op(const Node& n) {
                                   (const double*)host_arg(n, a[4]),
                                   (const float*)host_arg(n, a[5]), f[0], P<int>(a[6]),
                                   P<double>(a[7]), P<double>(a[8]), s);
+    case RV_SCHED_PREPROCESS_CHAIN:
+      // in, out, B, H, W, pitch, desc(host), ws, ws_bytes, lb_out, geo(host)
+      return rv_preprocess_chain_u8(P<const uint8_t>(a[0]), P<uint8_t>(a[1]), (int)a[2], (int)a[3],
+                                    (int)a[4], (int)a[5],
+                                    (const rv_chain_desc*)host_arg(n, a[6]), P<void>(a[7]),
+                                    (size_t)a[8], P<uint8_t>(a[9]),
+                                    (const int*)host_arg(n, a[10]), s);
   }
   set_error("rv_sched: unknown op %d", n.op);
   return RV_EINVAL;

@@ -48,6 +48,10 @@ _SIGS = {
     "rv_clahe_median_letterbox_fits": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "rv_gray_span_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
+    "rv_preprocess_chain_route": (c_int, [c_void_p, c_int, c_int, POINTER(c_int)]),
+    "rv_preprocess_chain_ws_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "rv_preprocess_chain_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_void_p, c_size_t, c_void_p, POINTER(c_int), c_void_p]),
     # result hand-back
     "rv_results_bytes": (c_size_t, [c_int, c_int]),
     "rv_results_handback": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
@@ -199,9 +203,9 @@ def check(status: int, what: str = "") -> None:
 # stream-ordered calls a launch schedule can record (rvs_amd.schedule._OPS)
 _RECORDABLE = {"rv_clahe_median_letterbox_u8", "rv_clahe_median_u8", "rv_letterbox_u8",
                "rv_yolo_forward_part", "rv_nms_postprocess", "rv_sort_update",
-               "rv_results_handback", "rv_untracked_metrics"}
+               "rv_results_handback", "rv_untracked_metrics", "rv_preprocess_chain_u8"}
 
-_NOCHECK = {"rv_sched_num_nodes", "rv_sched_event_query", "rv_abi_version", "rv_cand_segments", "rv_yolo_cand_segments", "rv_clahe_median_fits", "rv_clahe_median_letterbox_fits", "rv_yolo_num_convs", "rv_yolo_num_anchors",
+_NOCHECK = {"rv_preprocess_chain_route", "rv_sched_num_nodes", "rv_sched_event_query", "rv_abi_version", "rv_cand_segments", "rv_yolo_cand_segments", "rv_clahe_median_fits", "rv_clahe_median_letterbox_fits", "rv_yolo_num_convs", "rv_yolo_num_anchors",
             "rv_yolo_num_buffers", "rv_yolo_trace", "rv_yolo_profile_read", "rv_yolo_tuned_config",
             "rv_yolo_profile_bytes", "rv_yolo_profile_times", "rv_yolo_buffer_esize", "rv_yolo_conv_candidates"}
 

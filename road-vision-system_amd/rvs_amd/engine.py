@@ -120,6 +120,13 @@ class RoadVisionEngine:
         if self.fused_letterbox:
             return self.pipeline.run_with_letterbox(frames, self.detector.geo,
                                                     self.detector.lb[lb_slot][lb_off:lb_off + B])
+        if self.pipeline.chain_supported:
+            # any other chain of the built-in ops, the gate included: one
+            # stream-ordered library call (the gate is evaluated on the device)
+            if self.detector is None:
+                return self.pipeline.run_chain_with_letterbox(frames)
+            return self.pipeline.run_chain_with_letterbox(
+                frames, self.detector.geo, self.detector.lb[lb_slot][lb_off:lb_off + B])
         proc = self.pipeline(frames)
         if self.detector is None:
             return proc, None
@@ -134,9 +141,19 @@ class RoadVisionEngine:
             self.pipeline.run_with_letterbox(frames, self.detector.geo,
                                              self.detector.lb[lb_slot][lb_off:lb_off + B], out=proc)
             return
+        if self.pipeline.chain_supported:
+            if self.detector is None:
+                self.pipeline.run_chain_with_letterbox(frames, out=proc)
+            else:
+                self.pipeline.run_chain_with_letterbox(
+                    frames, self.detector.geo, self.detector.lb[lb_slot][lb_off:lb_off + B],
+                    out=proc)
+            return
         if _lib._recorder is not None:
-            raise RuntimeError("a recorded schedule needs the fused CLAHE+median+letterbox chain "
-                               "(the unfused chain allocates and copies with torch ops)")
+            raise RuntimeError("a recorded schedule needs a preprocess chain of the built-in ops "
+                               "(CLAHEDehaze / MedianDerain, at most 4): this chain has "
+                               f"{self.pipeline.unsupported_op}, which runs eagerly with torch "
+                               "allocations and copies")
         p, _ = self.preprocess_stage(frames, lb_slot, lb_off)
         proc.copy_(p)
 

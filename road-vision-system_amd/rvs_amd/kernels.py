@@ -6,6 +6,8 @@ tensors.  Nothing here copies to the host or synchronises.
 """
 from __future__ import annotations
 
+import ctypes
+import struct
 from typing import Optional, Tuple
 
 import torch
@@ -139,6 +141,94 @@ def clahe_median_letterbox_fits(H: int, W: int, tiles: int, k: int, geo) -> bool
 def clahe_median_fits(frames: torch.Tensor, tiles: int, k: int) -> bool:
     H, W = frames.shape[-3], frames.shape[-2]
     return bool(_lib.load().rv_clahe_median_fits(H, W, int(tiles), int(k)))
+
+
+CHAIN_DESC_BYTES = 120  # sizeof(rv_chain_desc), include/rvhip.h
+CHAIN_MAX_OPS = 4
+ROUTE_FUSED, ROUTE_FUSED_GATED, ROUTE_OPS = 0, 1, 2  # RV_CHAIN_ROUTE_*
+
+
+def chain_desc(ops, enabled: bool = True, gate_on: bool = False, contrast_thresh: float = 20.0):
+    """The host descriptor (rv_chain_desc) of a preprocess chain.  ops: a list
+    of ("clahe", space, tiles, clip) and ("median", k) tuples holding the
+    normalised parameters (preprocess.ops.clahe_params / median_ksize).
+    Nothing is validated here: the library checks the descriptor (n_ops,
+    tiles, k, ...) and answers RV_EINVAL."""
+    ops = list(ops)
+    blob = struct.pack("<iiiid", int(bool(enabled)), len(ops), int(bool(gate_on)), 0,
+                       float(contrast_thresh))
+    for op in (ops + [("median", 0)] * CHAIN_MAX_OPS)[:CHAIN_MAX_OPS]:
+        if op[0] == "clahe":
+            _, space, tiles, clip = op
+            blob += struct.pack("<iiiid", 0, 1 if str(space).upper() == "LAB" else 0, int(tiles), 0,
+                                float(clip))
+        elif op[0] == "median":
+            blob += struct.pack("<iiiid", 1, 0, 0, int(op[1]), 0.0)
+        else:
+            raise ValueError(f"chain op {op[0]!r}: expected 'clahe' or 'median'")
+    assert len(blob) == CHAIN_DESC_BYTES
+    return (ctypes.c_uint8 * CHAIN_DESC_BYTES).from_buffer_copy(blob)
+
+
+def preprocess_chain_route(desc, H: int, W: int, geo=None) -> int:
+    """Which route rv_preprocess_chain_u8 takes (ROUTE_*); a host query."""
+    st = int(_lib.load().rv_preprocess_chain_route(
+        desc, int(H), int(W), None if geo is None else _lib.int_array(geo)))
+    if st < 0:
+        _lib.check(st, "rv_preprocess_chain_route")
+    return st
+
+
+def preprocess_chain_ws_bytes(desc, B: int, H: int, W: int, pitch: Optional[int] = None) -> int:
+    """Workspace bytes of rv_preprocess_chain_u8 (0 for a bad descriptor); a
+    host query.  pitch: bytes per frame row (default 3 * W)."""
+    return int(_lib.load().rv_preprocess_chain_ws_bytes(
+        desc, int(B), int(H), int(W), 3 * int(W) if pitch is None else int(pitch)))
+
+
+def desc_is_identity(desc) -> bool:
+    """True for a disabled or empty chain: proc = raw for every frame."""
+    enabled, n_ops = struct.unpack_from("<ii", bytes(desc), 0)
+    return not enabled or n_ops == 0
+
+
+def _desc_has_lab(desc) -> bool:
+    b = bytes(desc)
+    n = min(struct.unpack_from("<i", b, 4)[0], CHAIN_MAX_OPS)
+    return any(struct.unpack_from("<ii", b, 24 + 24 * i) == (0, 1) for i in range(max(n, 0)))
+
+
+def preprocess_chain(frames: torch.Tensor, desc, geo=None, out: Optional[torch.Tensor] = None,
+                     lb_out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """pipeline(raw) + LetterBox of any built-in chain (rv_preprocess_chain_u8):
+    returns (proc, letterboxed proc), or (proc, None) when geo is None.
+    Stream-ordered launches only: the low-contrast gate is evaluated on the
+    device.  A disabled or empty chain called without `out` returns the
+    input frames themselves as proc (no copy), as the pipeline does."""
+    x, B, H, W, pitch = _frames(frames)
+    if out is None and desc_is_identity(desc):
+        if geo is None:
+            return frames, None
+        out, proc = None, frames
+    else:
+        out = proc = _like(x, out)
+        if frames.dim() != 4:
+            proc = out[0]
+    if geo is None:
+        if lb_out is not None:
+            raise ValueError("lb_out needs the letterbox geometry (geo)")
+    elif lb_out is None:
+        lb_out = torch.empty((B, geo[0], geo[1], 3), dtype=torch.uint8, device=x.device)
+    need = preprocess_chain_ws_bytes(desc, B, H, W, pitch)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    if _desc_has_lab(desc) and x.device not in _lab_ready:
+        with torch.cuda.device(x.device):  # one synchronous upload per device, never recorded
+            call("rv_lab_init")
+        _lab_ready.add(x.device)
+    call("rv_preprocess_chain_u8", ptr(x), ptr(out), B, H, W, pitch, desc, ptr(ws), ws.numel(),
+         ptr(lb_out), None if geo is None else _lib.int_array(geo), stream_ptr())
+    return proc, lb_out
 
 
 def gray_span(frames: torch.Tensor) -> torch.Tensor:

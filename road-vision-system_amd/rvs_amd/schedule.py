@@ -54,6 +54,7 @@ _OPS = {
     "rv_sort_update": (5, 16, {8: 48, 9: 72, 10: 8}),
     "rv_results_handback": (6, 10, {}),
     "rv_untracked_metrics": (7, 10, {4: 72, 5: 8}),
+    "rv_preprocess_chain_u8": (8, 11, {6: 120, 10: 24}),
 }
 _FLOAT = (ctypes.c_float, ctypes.c_double)
 

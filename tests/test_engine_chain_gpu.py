@@ -1,0 +1,151 @@
+"""Every built-in preprocess configuration on the recorded pipeline:
+PipelinedRun(mode="native") of an engine whose chain is not the fused default
+(ksize 5, LAB, the low-contrast gate, preprocess off, a one-op chain) against
+sequential step() calls of a second engine and against the oracle's chain;
+a chain holding a custom op still needs mode="eager"."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import cpu
+
+pytestmark = pytest.mark.gpu
+
+S, H, W, K = 3, 360, 640, 4
+IMG = [[560, 1000], [1360, 1000], [1160, 620], [760, 620]]
+WLD = [[-3.5, 5.0], [3.5, 5.0], [3.5, 30.0], [-3.5, 30.0]]
+
+
+def _cfg():
+    from rvs_amd.config import load_config
+    cfg = load_config()
+    cfg["geometry"]["enabled"] = True
+    cfg["geometry"]["projector"]["image_points"] = IMG
+    cfg["geometry"]["projector"]["world_points"] = WLD
+    return cfg
+
+
+def cpu_gray_span(img):
+    i = img.astype(np.int32)
+    g = (i[..., 0] * 1868 + i[..., 1] * 9617 + i[..., 2] * 4899 + 8192) >> 14
+    return int(g.max() - g.min())
+
+
+def _clahe(img):
+    return cpu.clahe_ycrcb(img, 8, 2.0)
+
+
+# name -> (edit of cfg["preprocess"], the oracle's chain on one frame, gate on)
+CONFIGS = {
+    "ksize5": (lambda p: p["chain"][1]["params"].update(ksize=5),
+               lambda f: cpu.median(_clahe(f), 5), False),
+    "lab": (lambda p: p["chain"][0]["params"].update(space="LAB"),
+            lambda f: cpu.median(cpu.clahe_lab(f, 8, 2.0), 3), False),
+    "gate": (lambda p: p.update(auto_gate={"enable_low_contrast_gate": True,
+                                           "contrast_thresh": 20.0}),
+             lambda f: cpu.median(_clahe(f), 3), True),
+    "disabled": (lambda p: p.update(enabled=False), lambda f: f, False),
+    "median_only": (lambda p: p.update(chain=[{"name": "MedianDerain", "params": {"ksize": 3}}]),
+                    lambda f: cpu.median(f, 3), False),
+}
+
+
+@pytest.fixture(scope="module")
+def inputs(cuda):
+    """K steps of S streams; a second set in which stream 1 is squeezed to a
+    low contrast on steps 1 and 2 only (for the gate).  Shared, never written."""
+    from rvs_amd.synth import road_frames
+    frames = road_frames(S, K, H, W, device=cuda)
+    gated = frames.clone()
+    for k in (1, 2):
+        f = gated[k, 1].to(torch.int32)
+        gated[k, 1] = (90 + torch.div(f - 90, 16, rounding_mode="floor")).clamp(0, 255).to(torch.uint8)
+    ts = [torch.full((S,), k / 30.0, dtype=torch.float64, device=cuda) for k in range(K)]
+    return frames, gated, ts
+
+
+def _key(res):
+    return [[(d.x1, d.y1, d.x2, d.y2, d.conf, d.cls_id, d.track_id, d.distance_m, d.speed_kmh)
+             for d in s] for s in res]
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_recorded_pipeline_runs_any_builtin_chain(cuda, inputs, name):
+    from rvs_amd.engine import RoadVisionEngine
+    from rvs_amd.schedule import PipelinedRun
+    edit, ref, gate = CONFIGS[name]
+    cfg = copy.deepcopy(_cfg())
+    edit(cfg["preprocess"])
+    frames = inputs[1] if gate else inputs[0]
+    ts = inputs[2]
+    host = frames.cpu().numpy()
+    low = [[cpu_gray_span(host[k, s]) < 20.0 for s in range(S)] for k in range(K)]
+    if gate:  # the fixture has the intended pattern before any GPU output is looked at
+        assert low == [[False] * 3, [False, True, False], [False, True, False], [False] * 3]
+    want_proc = [np.stack([ref(host[k, s]) if (low[k][s] or not gate) else host[k, s]
+                           for s in range(S)]) for k in range(K)]
+
+    seq = RoadVisionEngine(cfg, S, (H, W), device=cuda)
+    assert not seq.fused_letterbox and seq.pipeline.chain_supported
+    seq_res, seq_proc = [], []
+    for r in range(2):
+        for k in range(K):
+            out = seq.step(frames[k], ts[k])
+            seq_res.append(_key(seq.results(out)))
+            seq_proc.append(out["proc"].cpu().numpy())
+    for k in range(K):
+        np.testing.assert_array_equal(seq_proc[k], want_proc[k], err_msg=f"step() proc {k}")
+
+    pip = RoadVisionEngine(cfg, S, (H, W), device=cuda, lanes=2, pair=2)
+    run = PipelinedRun(pip, [frames[k] for k in range(K)], ts, mode="native")
+    assert run.sched.num_nodes() > 0
+    for r in range(2):  # the second run replays the recorded descriptor and geometry
+        run.run()
+        torch.cuda.synchronize()
+        for k, o in enumerate(run.outs):
+            assert _key(pip.results(o)) == seq_res[r * K + k], f"run {r} step {k}"
+            np.testing.assert_array_equal(o["proc"].cpu().numpy(), want_proc[k],
+                                          err_msg=f"run {r} proc {k}")
+            np.testing.assert_array_equal(o["proc"].cpu().numpy(), seq_proc[r * K + k])
+    assert sum(len(s) for r in seq_res for s in r) > 0  # the comparison saw detections
+    np.testing.assert_array_equal(frames.cpu().numpy(), host)  # inputs untouched
+    run.close()
+    seq.close()
+    pip.close()
+
+
+def test_custom_op_chain_needs_eager_mode(cuda, inputs):
+    """A chain with an op the library does not know cannot be recorded (the
+    error names the op); mode="eager" still runs it."""
+    from rvs_amd.engine import RoadVisionEngine
+    from rvs_amd.preprocess import registry
+    from rvs_amd.preprocess.base import PreprocessOp
+    from rvs_amd.schedule import PipelinedRun
+
+    class Invert(PreprocessOp):
+        def __call__(self, image):
+            return 255 - image
+
+    frames, _, ts = inputs
+    cfg = copy.deepcopy(_cfg())
+    cfg["preprocess"]["chain"] = [{"name": "MedianDerain", "params": {"ksize": 3}},
+                                  {"name": "Invert", "params": {}}]
+    registry.REGISTRY["Invert"] = Invert
+    try:
+        eng = RoadVisionEngine(cfg, S, (H, W), device=cuda, lanes=2, pair=2)
+        assert not eng.pipeline.chain_supported
+        with pytest.raises(RuntimeError, match="Invert"):
+            PipelinedRun(eng, [frames[k] for k in range(K)], ts, mode="native")
+        run = PipelinedRun(eng, [frames[k] for k in range(K)], ts, mode="eager")
+        run.run()
+        torch.cuda.synchronize()
+        host = frames.cpu().numpy()
+        for k, o in enumerate(run.outs):
+            want = np.stack([255 - cpu.median(host[k, s], 3) for s in range(S)])
+            np.testing.assert_array_equal(o["proc"].cpu().numpy(), want)
+        run.close()
+        eng.close()
+    finally:
+        del registry.REGISTRY["Invert"]
