@@ -264,7 +264,27 @@ int rv_yolo_destroy(void* handle);
  * optional bf16 residual view of the output's shape.  w: packed
  * [Cout_pad16][k*k][Cin_pad32] bf16, bias: f32 [Cout_pad16].  cfg6
  * (nullable): {MR, NR, G, resw, persist, kind} as rv_yolo_tuned_config
- * reports; RV_EINVAL when it is not valid for the layer. */
+ * reports; RV_EINVAL when it is not valid for the layer.
+ *
+ * in / out / res may be channel slices of wider NHWC tensors: the pointer
+ * is the slice's first channel of pixel 0 and in_cs / out_cs / res_cs the
+ * wide tensor's channel count (elements per pixel).  Supported, and checked
+ * before anything is launched (RV_EINVAL otherwise, nothing written):
+ *   - input side, read with 16-byte loads of 8 channels: Cin % 8 == 0,
+ *     in_cs % 8 == 0, `in` 16-byte aligned (a slice offset of whole 8
+ *     channels).  Only channels [0, Cin) of the view are read, so whatever
+ *     the wide tensor's other channels hold (NaN included) has no effect;
+ *   - output side, written with 8-byte stores of 4 channels (16-byte stores
+ *     of 8 where Cout % 16 == 0, at 8-byte alignment): Cout % 4 == 0,
+ *     out_cs % 4 == 0, `out` 8-byte aligned (a slice offset of whole 4
+ *     channels).  Only channels [0, Cout) of the view are written;
+ *   - residual, read with 8-byte loads of 4 channels: res_cs % 4 == 0, `res`
+ *     8-byte aligned; it must not overlap the channels the call writes;
+ *   - w and bias 16-byte aligned, padded as above (rows >= Cout and input
+ *     channels >= Cin of w zero);
+ *   - B * Hin * Win * in_cs, * out_cs and * res_cs each below 2^31.
+ * A 1x1 stride-2 conv has no LDS-staged configuration (every cfg6 is
+ * rejected for it) and runs the generic kernel. */
 int rv_conv_bf16(const void* in, int B, int Hin, int Win, int Cin, int in_cs, const void* w,
                  const float* bias, int Cout, int k, int stride, void* out, int out_cs,
                  const void* res, int res_cs, int act, const int* cfg6, void* stream);

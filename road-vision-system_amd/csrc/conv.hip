@@ -14,6 +14,7 @@
 // fallback for the shapes rv_conv_bf16 supports but the patch kernel has no
 // configuration for (a 1x1 stride-2 conv, images of Hin*Win >= 2^24 pixels).
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include "conv.h"
@@ -1858,7 +1859,8 @@ static int try_launch_patch(const ConvArgs& a, hipStream_t s, int* st) {
 // of the output's shape) through the production launcher, for layer tests:
 // the weights packed as yolo.hip packs them ([Cout_pad16][k*k][Cin_pad32]
 // bf16), the bias padded to Cout_pad16.  cfg6 (nullable): an explicit
-// {MR, NR, G, resw, persist, kind} configuration.
+// {MR, NR, G, resw, persist, kind} configuration.  The supported channel
+// counts, strides and alignments are checked here (include/rvhip.h).
 }  // namespace rv
 extern "C" int rv_conv_bf16(const void* in, int B, int Hin, int Win, int Cin, int in_cs,
                             const void* w, const float* bias, int Cout, int k, int stride, void* out,
@@ -1869,6 +1871,22 @@ extern "C" int rv_conv_bf16(const void* in, int B, int Hin, int Win, int Cin, in
   RV_CHECK_ARG(B >= 1 && Hin >= 1 && Win >= 1 && Cin >= 1 && Cout >= 1, "bad shape");
   RV_CHECK_ARG((k == 1 || k == 3) && (stride == 1 || stride == 2), "k %d stride %d", k, stride);
   RV_CHECK_ARG(in_cs >= Cin && out_cs >= Cout && (!res || res_cs >= Cout), "channel strides");
+  // the kernels' access widths (include/rvhip.h): 16-byte input loads of 8
+  // channels, 8-byte output stores / residual loads of 4 channels
+  RV_CHECK_ARG(Cin % 8 == 0 && in_cs % 8 == 0 && (uintptr_t)in % 16 == 0,
+               "input: Cin %d and in_cs %d must be multiples of 8, in 16-byte aligned", Cin, in_cs);
+  RV_CHECK_ARG(Cout % 4 == 0 && out_cs % 4 == 0 && (uintptr_t)out % 8 == 0,
+               "output: Cout %d and out_cs %d must be multiples of 4, out 8-byte aligned", Cout,
+               out_cs);
+  RV_CHECK_ARG(!res || (res_cs % 4 == 0 && (uintptr_t)res % 8 == 0),
+               "residual: res_cs %d must be a multiple of 4, res 8-byte aligned", res_cs);
+  RV_CHECK_ARG((uintptr_t)w % 16 == 0 && (uintptr_t)bias % 16 == 0,
+               "w and bias must be 16-byte aligned");
+  // 32-bit element indices in the kernels
+  RV_CHECK_ARG((double)B * Hin * Win * in_cs < 2147483648.0 &&
+                   (double)B * Hin * Win * out_cs < 2147483648.0 &&
+                   (!res || (double)B * Hin * Win * res_cs < 2147483648.0),
+               "view of B=%d %dx%d pixels exceeds 2^31 elements", B, Hin, Win);
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.in = (const bf16_t*)in;

@@ -253,7 +253,9 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B,
           for (int m = 0; m < 5; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
           for (int k = 0; k < cinp; k += 32) {
             const bool kv = ok && k + quad * 8 < L.cin_c;
-            const uint4 bv = kv ? *(const uint4*)(fp + 4 * REG + k) : make_uint4(0, 0, 0, 0);
+            // the class features follow the box branch's cin_b channels in a
+            // feature row (80 in YOLOv8x; 4 * REG = 64 in the other variants)
+            const uint4 bv = kv ? *(const uint4*)(fp + L.cin_b + k) : make_uint4(0, 0, 0, 0);
             const bf16x8 Bf = __builtin_bit_cast(bf16x8, bv);
 #pragma unroll
             for (int m = 0; m < 5; ++m) {

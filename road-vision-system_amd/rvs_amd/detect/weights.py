@@ -113,6 +113,11 @@ def synthetic_weights(variant: int, seed: int = 0) -> np.ndarray:
     rng = np.random.default_rng(seed)
     parts = []
     with np.load(_CALIB, allow_pickle=False) as cal:
+        have = sorted({k.split("/")[0] for k in cal.files})
+        if str(variant) not in have:
+            raise ValueError(f"no synthetic calibration for YOLOv8 variant {variant} in "
+                             f"{os.path.basename(_CALIB)} (it has variants {', '.join(have)}); "
+                             f"tests/golden/make_yolo_scales.py {variant} produces the arrays")
         smooth = float(cal[f"{variant}/smooth"]) if f"{variant}/smooth" in cal.files else 0.0
         for i, (name, cin, cout, k, s, act) in enumerate(conv_list(variant)):
             w, b = base_weights(rng, seed, i, cin, cout, k, smooth)

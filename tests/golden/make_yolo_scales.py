@@ -136,7 +136,8 @@ if __name__ == "__main__":
         with np.load(OUT, allow_pickle=False) as old:
             arrays = {k: old[k] for k in old.files if int(k.split("/")[0]) not in variants}
     for v in variants:
-        hw = GEOMETRY[v]
+        hw = GEOMETRY.get(v, GEOMETRY[0])  # variants without an entry: n's choices
+        SMOOTH.setdefault(v, 0.0)
         cal = calibrate(v, H=hw[0], W=hw[1], mu=MU, box_std=0.7, target_cand=0.012,
                         road_prior=3.0, smooth=SMOOTH[v])
         for n, (sc, sh) in cal.items():

@@ -136,3 +136,29 @@ def test_missing_keys_raise():
     del sd["model.4.m.1.cv2.conv.weight"]
     with pytest.raises(KeyError, match="model.4.m.1.cv2"):
         flat_from_state_dict(sd, 0)
+
+
+@pytest.mark.parametrize("variant", [1, 3, 4])
+def test_synthetic_weights_without_calibration_names_the_variant(variant):
+    """synthetic_calib.npz holds arrays for n and m only: the other variants
+    get a ValueError that names the variant and the script that produces the
+    arrays, not a KeyError from the .npz lookup."""
+    from rvs_amd.detect.weights import synthetic_weights
+    with pytest.raises(ValueError, match=rf"variant {variant}\b.*make_yolo_scales\.py"):
+        synthetic_weights(variant)
+
+
+@pytest.mark.parametrize("variant", [1, 3, 4])
+def test_one_pass_normalisation_keeps_activations_in_range(variant):
+    """tests/yolo_synth.py (the GPU variant tests' weights) on YOLOv8s, l and
+    x at the tests' 160x224 geometry, judged by the f32 oracle alone: every SiLU conv's
+    pre-activation std within [0.5, 2], and between 0.5 % and 20 % of the
+    anchors candidates, so decode and candidate checks see both outcomes."""
+    import yolo_synth
+    lb = yolo_synth.letterboxed(160, 224, 2, 224)
+    assert lb.shape == (2, 160, 224, 3)
+    flat = yolo_synth.synth_weights_on(variant, lb)
+    stds, frac = yolo_synth.oracle_stats(variant, flat, lb)
+    assert len(stds) == len(yolo_ref.conv_specs(variant)[0]) - 6
+    assert all(0.5 <= lo and hi <= 2.0 for lo, hi in stds.values()), stds
+    assert 0.005 <= frac <= 0.20

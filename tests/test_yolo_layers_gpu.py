@@ -101,6 +101,12 @@ def _setup(cuda, H, W, B, variant=0):
 def test_every_conv_layerwise(cuda, H, W, B, variant):
     eng, ins, specs, params, lb, raw = _setup(cuda, H, W, B, variant)
     assert len(ins.recs) == len(specs) - 1  # all but model.0 go through conv_mfma
+    check_every_conv(ins, specs, params)
+
+
+def check_every_conv(ins, specs, params):
+    """Every traced conv of the last (unfused, raw) forward against float64
+    on the GPU's own inputs (shared with test_yolo_variants_gpu.py)."""
     worst = []
     for r in ins.recs:
         (ci_, inb, incs, inco, Hin, Win, Ho, Wo, o0, o0cs, o0co, up0, o1, o1cs, o1co, up1,
@@ -142,6 +148,7 @@ def test_every_conv_layerwise(cuda, H, W, B, variant):
                     part = g1[:, dy::2, dx::2] if up1 else g1
                     np.testing.assert_array_equal(part, got, err_msg=name)
     print("worst layers:", sorted(worst)[-3:])
+    return sorted(worst)[-3:]
 
 
 def test_first_conv_sppf_and_decode(cuda):
@@ -333,7 +340,21 @@ def test_residual_conv_exact_allocation(cuda, cfg):
     assert (d <= 2 * ulp_bf16(ref) + 1e-3 * rms).all()
 
 
-@pytest.mark.parametrize("H,W,B,variant", [(1080, 1920, 3, 0), (640, 640, 1, 0), (360, 640, 2, 0)])
+def _zero_candidate_launches(eng):
+    """Launches of the last forward without a conv configuration: the fused
+    C2f chains (rv_yolo_conv_candidates reports none for them)."""
+    from rvs_amd import _lib
+    lib, n, idx = _lib.load(), 0, 0
+    while True:
+        c = lib.rv_yolo_conv_candidates(eng._h, idx, None, 0)
+        if c < 0:  # one past the last launch
+            return n, idx
+        n += c == 0
+        idx += 1
+
+
+@pytest.mark.parametrize("H,W,B,variant", [(1080, 1920, 3, 0), (640, 640, 1, 0), (360, 640, 2, 0),
+                                            (160, 224, 2, 1)])  # 1 = YOLOv8s: a width-32 model.2
 def test_fused_c2f_is_bit_identical(cuda, H, W, B, variant):
     """The fused C2f chains (c2f.hip: model.2 / model.4 / model.15 bottlenecks
     + cv2 in one launch each, intermediates in LDS) against one launch per
@@ -343,18 +364,27 @@ def test_fused_c2f_is_bit_identical(cuda, H, W, B, variant):
     RV_YOLO_OPT_C2F_TAP_PAIRS = 0)."""
     from rvs_amd.detect import weights
     from rvs_amd.detect.yolo_hip import YoloEngine
-    eng = YoloEngine(variant, weights.synthetic_weights(variant, seed=5), B, (H, W), device=cuda)
     fr = np.stack([cpu.median(cpu.clahe_ycrcb(road_frame(H, W, seed=90 + b)), 3) for b in range(B)])
+    imgsz = min(640, max(H, W))
+    if variant in (0, 2):
+        flat = weights.synthetic_weights(variant, seed=5)
+    else:  # no shipped calibration: normalised on this test's own input
+        import yolo_synth
+        g = cpu.letterbox_geometry(H, W, imgsz)
+        flat = yolo_synth.synth_weights_on(variant, np.stack([cpu.letterbox(f, g) for f in fr]), seed=5)
+    eng = YoloEngine(variant, flat, B, (H, W), imgsz=imgsz, device=cuda)
     lb = eng.letterbox(torch.from_numpy(fr).to(cuda))
     eng.set_raw_fused(True)
     eng.set_c2f_tap_pairs(False)
     outs = []
+    nfused = []
     for fuse in (False, True):
         eng.set_fuse_c2f(2 if fuse else 0)  # every fusable chain (the default fuses C = 16 only)
         raw = torch.full((B, 84, eng.A), float("nan"), dtype=torch.float32, device=cuda)
         eng.forward_raw(lb, raw, slot=int(fuse))
         torch.cuda.synchronize()
         ins = Introspect(eng, B)
+        nfused.append(_zero_candidate_launches(eng))
         # outputs of the fused blocks: X2 (model.2), the CAT14 slice of model.4,
         # X15 (model.15) -- located through the trace of the last forward
         specs, _ = yolo_ref.conv_specs(variant)
@@ -367,6 +397,10 @@ def test_fused_c2f_is_bit_identical(cuda, H, W, B, variant):
         outs.append((raw.cpu().numpy(), maps, seg))
     (r0, m0, s0), (r1, m1, s1) = outs
     assert set(m0) == {"model.2.cv2", "model.4.cv2", "model.15.cv2"} == set(m1)
+    # the second forward did fuse: chains replace several launches each (which
+    # blocks fuse depends on the variant's widths; the maps above are compared
+    # either way)
+    assert nfused[1][0] > nfused[0][0] and nfused[1][1] < nfused[0][1], nfused
     for k in m0:
         np.testing.assert_array_equal(m1[k], m0[k], err_msg=k)
     np.testing.assert_array_equal(r1, r0)
