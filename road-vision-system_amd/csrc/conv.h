@@ -1,8 +1,8 @@
 // Internal interface of the YOLOv8 conv / pool / head kernels (conv.hip,
-// sppf.hip, detect.hip, stem.hip, c2f.hip) used by the model plan (yolo.hip).  Activations are NHWC bf16 (raw uint16 bits);
-// a "view" is (base pointer, channel stride of the buffer, channel offset),
-// so concatenation is free: producers write into a slice of a wider buffer
-// and consumers read a slice.
+// sppf.hip, detect.hip, stem.hip, c2f.hip) used by the model plan (yolo.hip).
+// Activations are NHWC bf16 (raw uint16 bits); a "view" is (base pointer,
+// channel stride of the buffer, channel offset), so concatenation is free:
+// producers write into a slice of a wider buffer and consumers read a slice.
 #pragma once
 #include "common.h"
 
@@ -38,7 +38,7 @@ struct ConvArgs {
   int g2_cout0, g2_in_co, g2_Cin;
   const bf16_t* g2_w;
   const float* g2_bias;
-  // > 0: this launch record stands for a fused C2f chain (yolo.hip's
+  // > 0: this launch record stands for a fused C2f chain (yolo_model.h's
   // Model::fused[fused - 1]); the autotuner leaves it alone
   int fused;
   // fp8 (OCP e4m3fn) path: in8 = 1 -> the input (and residual) views hold
@@ -88,7 +88,7 @@ int conv_candidates(const ConvArgs& a, ConvCfg* out, int cap);
 // First conv (3 -> C0, k3 s2, p1) straight from the u8 BGR letterboxed
 // frame (the reference's predictor preprocess im[..., ::-1] / 255 folded into
 // the weights), on i8 MFMAs over the window bytes with exact i32 sums; the
-// weights in the integer form yolo.hip's packer writes (pack_conv0q).
+// weights in the integer form yolo_def.hip's packer writes (pack_conv0q).
 struct Conv0Q {
   const int8_t* d;   // [3][C0][64] balanced base-256 digits of Q (k = 16 ky + 3 kx + ch, BGR)
   const float* s;    // [C0] value scale

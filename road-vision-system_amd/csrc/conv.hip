@@ -1857,7 +1857,7 @@ static int try_launch_patch(const ConvArgs& a, hipStream_t s, int* st) {
 
 // One bf16 conv (k 1 or 3, pad k / 2, SiLU optional, optional bf16 residual
 // of the output's shape) through the production launcher, for layer tests:
-// the weights packed as yolo.hip packs them ([Cout_pad16][k*k][Cin_pad32]
+// the weights packed as yolo_def.hip packs them ([Cout_pad16][k*k][Cin_pad32]
 // bf16), the bias padded to Cout_pad16.  cfg6 (nullable): an explicit
 // {MR, NR, G, resw, persist, kind} configuration.  The supported channel
 // counts, strides and alignments are checked here (include/rvhip.h).

@@ -23,7 +23,7 @@ namespace rv {
 // dword loads, three v_alignbyte_b32 and an XOR 0x80 each (u8 x -> i8
 // x - 128): no per-byte conversion.  The weights are the integers Q =
 // round(V / s) of V = w[rgb][ky][kx] / 255 at 2^-23 of the channel's largest
-// |V| (yolo.hip pack_conv0q) in three balanced base-256 i8 digits, one MFMA
+// |V| (yolo_def.hip pack_conv0q) in three balanced base-256 i8 digits, one MFMA
 // each, the accumulator started at 128 sum_k D_i[k] so it ends at
 // T_i = sum_k D_i[k] x[k] exactly (< 2^24, exact in f32).  The value is
 // s (65536 T0 + (256 T1 + T2)) + b in f32, with 256 T1 + T2 summed exactly in

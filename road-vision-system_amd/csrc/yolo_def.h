@@ -1,0 +1,59 @@
+// YOLOv8 model definition (yolo_def.hip): the canonical conv list of a
+// variant (Ultralytics state_dict order, BN already fused into conv weight +
+// bias) and the layout of its packed weight blob.  Host code only.
+#pragma once
+#include <string>
+#include <vector>
+#include "conv.h"
+
+namespace rv {
+
+struct ConvSpec {
+  std::string name;
+  int cin, cout, k, s, act;
+  size_t w_off = 0, b_off = 0;  // byte offsets in the packed blob
+  size_t ws_off = 0;            // fp8 convs: per-cout weight scales (f32)
+  bool f8 = false;              // fp8 weights / inputs (RV_YOLO_DTYPE_FP8 plans)
+};
+
+struct Variant {
+  int c1, c2, c3, c4, c5;   // backbone widths (P1..P5)
+  int h12, h15, h18, h21;   // head widths
+  int nb, nm;               // C2f repeats for "3" and "6"
+  int c2d, c3d;             // Detect branch widths
+  int nc = 80, reg = 16;
+};
+
+struct ModelDef {
+  Variant v;
+  int dtype = 0;  // RV_YOLO_DTYPE_BF16 / RV_YOLO_DTYPE_FP8
+  std::vector<ConvSpec> convs;
+  // conv 0's integer form (the i8 MFMA conv0, conv.h Conv0Q), after every
+  // conv's block: digits [3][C0][64] i8, scales [C0] f32, biases [C0] f32,
+  // accumulator starts [3][C0] i32
+  size_t q_off = 0, q_bytes = 0;
+  int add(const std::string& n, int ci, int co, int k, int s, int act = 1) {
+    convs.push_back(ConvSpec{n, ci, co, k, s, act});
+    return (int)convs.size() - 1;
+  }
+  void c2f(const std::string& p, int c1, int c2, int n) {
+    const int c = c2 / 2;
+    add(p + ".cv1", c1, 2 * c, 1, 1);
+    add(p + ".cv2", (2 + n) * c, c2, 1, 1);
+    for (int i = 0; i < n; ++i) {
+      add(p + ".m." + std::to_string(i) + ".cv1", c, c, 3, 1);
+      add(p + ".m." + std::to_string(i) + ".cv2", c, c, 3, 1);
+    }
+  }
+  int find(const std::string& n) const {
+    for (size_t i = 0; i < convs.size(); ++i)
+      if (convs[i].name == n) return (int)i;
+    return -1;
+  }
+};
+
+bool build_def(int variant, ModelDef& m, int dtype = RV_YOLO_DTYPE_BF16);
+size_t packed_bytes(const ModelDef& m);
+size_t flat_floats(const ModelDef& m);
+
+}  // namespace rv

@@ -1,7 +1,7 @@
 """YOLOv8 weights for the HIP detector.
 
 The conv list (names, shapes, order) comes from the native plan in
-csrc/yolo.hip (rv_yolo_conv_info) -- Ultralytics state_dict order with BN
+csrc/yolo_def.hip (rv_yolo_conv_info) -- Ultralytics state_dict order with BN
 fused.  Real checkpoints are not available in this environment
 (.MISSING_LARGE_BLOBS:1 lists yolov8n.pt; there is no network), so weights are
 either loaded from a local Ultralytics state_dict (load_weights: .safetensors,

@@ -26,6 +26,10 @@ from .weights import COCO80, DTYPES, pack, variant_of, weights_from_config
 
 CAND_BYTES = 32
 
+# rv_yolo_set_option numbers (include/rvhip.h RV_YOLO_OPT_*)
+OPT_RAW_UNFUSED, OPT_FUSE_C2F, OPT_STEM_X1, OPT_HEAD_STREAMS, OPT_FUSE_CV1 = 1, 2, 3, 4, 5
+OPT_C2F_TAP_PAIRS = 7
+
 
 def scale_boxes_params(img1_hw, img0_hw):
     """Ultralytics ops.scale_boxes(img1_shape, boxes, img0_shape) constants:
@@ -199,48 +203,45 @@ class YoloEngine:
         except Exception:
             pass
 
+    def _set_option(self, opt: int, value: int) -> None:
+        for h in self._hs:  # every forward context runs the same plan
+            call("rv_yolo_set_option", h, opt, int(value))
+
     def set_raw_fused(self, fused: bool) -> None:
         """Raw forwards run the production kernel sequence (fused stem) when
         True, so forward_raw(raw) reproduces the candidate path's prediction
         exactly; False (default) keeps every activation for layer tests."""
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 1, 0 if fused else 1)
+        self._set_option(OPT_RAW_UNFUSED, 0 if fused else 1)
 
     def set_stem_x1(self, on: bool) -> None:
         """The fused stem also writes the X1 map (RV_YOLO_OPT_STEM_X1; by
         default X1 stays in registers when model.2.cv1 is fused into it)."""
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 3, 1 if on else 0)
+        self._set_option(OPT_STEM_X1, 1 if on else 0)
 
     def set_head_streams(self, on: bool) -> None:
         """The P3 / P4 Detect heads on the handle's two side streams (True,
         default) or on the caller's stream (RV_YOLO_OPT_HEAD_STREAMS)."""
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 4, 1 if on else 0)
+        self._set_option(OPT_HEAD_STREAMS, 1 if on else 0)
 
     def set_fuse_cv1(self, on: bool) -> None:
         """model.3 and model.4.cv1 as one launch with the 1x1 chained on
         model.3's output tile in LDS (True, default) or as two launches
         (RV_YOLO_OPT_FUSE_CV1; bit-identical results)."""
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 5, 1 if on else 0)
+        self._set_option(OPT_FUSE_CV1, 1 if on else 0)
 
     def set_c2f_tap_pairs(self, on: bool) -> None:
         """The fused width-16 C2f chain's 3x3 convs on tap pairs (True,
         default: within 1 bf16 ulp of the per-tap k order) or one k-step per
         tap (False: bit-identical to the unfused launches;
         RV_YOLO_OPT_C2F_TAP_PAIRS)."""
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 7, 1 if on else 0)
+        self._set_option(OPT_C2F_TAP_PAIRS, 1 if on else 0)
 
     def set_fuse_c2f(self, on) -> None:
         """Narrow C2f blocks as one fused launch or one launch per conv
         (RV_YOLO_OPT_FUSE_C2F; bit-identical results): True / 1 = the
         hidden-width-16 chains only (default), 2 = widths 16 and 32,
         False / 0 = none."""
-        v = 1 if on is True else (0 if on is False else int(on))
-        for h in self._hs:
-            call("rv_yolo_set_option", h, 2, v)
+        self._set_option(OPT_FUSE_C2F, 1 if on is True else (0 if on is False else int(on)))
 
     def letterbox(self, frames: torch.Tensor, slot: int = 0, off: int = 0) -> torch.Tensor:
         """Letterbox into images [off, off + B) of letterbox slot `slot`."""
@@ -251,8 +252,10 @@ class YoloEngine:
                     candidates: bool = True, slot: int = 0, lane: int = 0, part: int = 0,
                     batch: Optional[int] = None):
         """YOLOv8 forward + decode in forward context `lane`; candidates go to
-        candidate slot `slot`.  part 1 / 2: the two halves of the forward
-        (rv_yolo_forward_part; part 2 takes no letterbox, `batch` gives B)."""
+        candidate slot `slot`.  part 1 / 2: the two halves of the forward;
+        part 3 / 4: part 1 again in two (stem .. model.2, model.3 .. model.15)
+        (rv_yolo_forward_part; parts 2 and 4 take no letterbox, `batch` gives
+        B)."""
         B = lb.shape[0] if lb is not None else int(batch)
         if B > self.max_batch:
             raise ValueError(f"batch {B} > max_batch {self.max_batch}")
@@ -275,10 +278,7 @@ class YoloEngine:
         call("rv_yolo_autotune", self._h, ptr(lb), B, ptr(self.ws), self.ws_bytes, int(reps),
              1 if verify else 0, ctypes.byref(bad), stream_ptr())
         if self.lanes > 1:  # the other forward contexts run the same plan
-            cfgs = self.tuned_configs()
-            for h in self._hs[1:]:
-                for i, c in enumerate(cfgs):
-                    call("rv_yolo_set_tuned", h, len(cfgs), i, _lib.int_array(c))
+            self.load_tuned(self.tuned_configs(), self._hs[1:])
         return bad.value
 
     def tuned_configs(self):
@@ -303,11 +303,12 @@ class YoloEngine:
         call("rv_yolo_conv_candidates", self._h, int(idx), buf, n)
         return [tuple(buf[6 * i:6 * i + 6]) for i in range(n)]
 
-    def load_tuned(self, cfgs) -> None:
+    def load_tuned(self, cfgs, handles=None) -> None:
         """Install saved per-launch configurations (tuned_configs() of an
-        earlier autotune of the same plan) instead of autotuning."""
+        earlier autotune of the same plan) instead of autotuning, in every
+        forward context (or the given handles)."""
         n = len(cfgs)
-        for h in self._hs:
+        for h in self._hs if handles is None else handles:
             for i, c in enumerate(cfgs):
                 call("rv_yolo_set_tuned", h, n, i, _lib.int_array(c))
 
