@@ -307,6 +307,42 @@ int rv_yolo_pack2(int variant, int dtype, const float* flat, size_t n, void* hos
                   size_t out_bytes);
 int rv_yolo_create2(int variant, int dtype, const void* dev_packed, int max_B, int in_h, int in_w,
                     void** handle);
+
+/* Custom class counts (a YOLOv8 fine-tuned on nc classes; the reference takes
+ * nc from the checkpoint, src/detect/yolo_ultralytics.py:16-24).  Every entry
+ * above that takes no nc means nc = 80 and is unchanged.  1 <= nc <= 128 (the
+ * NMS class mask is 4 x 32 bits); outside it the call returns RV_EINVAL (the
+ * size_t entries 0), rv_last_error names the range and nothing is written.
+ * fp8 plans exist for nc = 80 only: rv_yolo_pack3 / rv_yolo_create3 refuse
+ * RV_YOLO_DTYPE_FP8 with another nc (RV_EINVAL).
+ *
+ * Shapes: rv_yolo_conv_info_nc and the flat layout are the Ultralytics
+ * state_dict's own: the Detect class branch is c3d = max(h15, min(nc, 100))
+ * wide (h15: the P3 width of the variant) and model.22.cv3.i.2 maps c3d -> nc.
+ * Padding contract (internal, visible only through the introspection
+ * entries): the plan runs the class branch padded to a multiple of 8
+ * channels -- the "DA<i>" / "DB<i>" buffers are c2d + pad8(c3d) wide -- and
+ * the f32 logits buffers "HD<i>" have rows of pad4(64 + nc) floats.  The
+ * packed rows / columns behind the padding are zero, so every padding channel
+ * of those buffers is exactly 0 after a forward and every logical channel is
+ * the sum it would be without padding.  nc itself is exact everywhere else:
+ * raw_out is (B, 4 + nc, A) dense, candidate classes are < nc. */
+int rv_yolo_num_convs_nc(int variant, int nc);
+int rv_yolo_conv_info_nc(int variant, int nc, int idx, int* info, char* name, int name_cap);
+size_t rv_yolo_flat_floats_nc(int variant, int nc);
+size_t rv_yolo_packed_bytes3(int variant, int dtype, int nc);
+int rv_yolo_pack3(int variant, int dtype, int nc, const float* flat, size_t n, void* host_out,
+                  size_t out_bytes);
+int rv_yolo_create3(int variant, int dtype, int nc, const void* dev_packed, int max_B, int in_h,
+                    int in_w, void** handle);
+int rv_yolo_num_classes(void* handle);
+/* Decode form of the handle's last forward that ran the decode (-1 before
+ * one): 0 = unfused last head stage, f32 logits read from HBM; 1 = last stage
+ * fused into the decode, class scan over the logits tile in LDS (any plan;
+ * always with raw_out); 2 = fused with the class scores kept in registers
+ * (YOLOv8n, nc = 80 or nc <= 64, no raw_out).  For tests that must prove
+ * which kernel ran. */
+int rv_yolo_head_form(void* handle);
 /* scales[n]: one per activation buffer (n = rv_yolo_num_buffers; entries of
  * bf16 / f32 buffers are ignored), each a positive power of two. */
 int rv_yolo_set_act_scales(void* handle, const float* scales, int n);

@@ -145,7 +145,8 @@ bool c2f_fusable(int C, int N, int cat_cs, int cat_co, int out_cs, int out_co);
 int launch_c2f_chain(const C2fArgs& a, int C, int N, bool shortcut, hipStream_t s);
 
 struct HeadLevel {
-  const float* logits;  // [B][H][W][cs] f32: [0,4*reg) box bins, [4*reg, 4*reg+nc) classes
+  const float* logits;  // [B][H][W][cs] f32: [0,4*reg) box bins, [4*reg, 4*reg+nc) classes,
+                        // then zeros up to cs (a multiple of 4)
   int H, W, cs;
   float stride;
   // fused form (feat != nullptr): the last 1x1 convs of the level run inside
@@ -170,9 +171,14 @@ struct Cand {  // one detection candidate (Ultralytics NMS row before NMS)
 // reference's raw output (B, 4+nc, A) and every anchor whose best class
 // score > conf as a candidate row: segment j (64 consecutive anchors of one
 // level) fills cand[b][64 j ...] in anchor order, its count in
-// seg_n[b][j] (nseg = decode_segments()).
+// seg_n[b][j] (nseg = decode_segments()).  The logits row stride cs of every
+// level is 4 * reg_max + nc padded to a multiple of 4; nc itself stays exact
+// (class scan, raw).  form (nullable) receives the kernel form launched: 0 =
+// logits read from HBM, 1 = fused last stage with the class scan in LDS, 2 =
+// fused with register-resident class scores.
 int decode_segments(const HeadLevel* lv, int nlv);
 int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_max, float conf,
-                         float* raw, Cand* cand, int cand_cap, int* seg_n, hipStream_t s);
+                         float* raw, Cand* cand, int cand_cap, int* seg_n, hipStream_t s,
+                         int* form = nullptr);
 
 }  // namespace rv

@@ -19,7 +19,10 @@ struct HeadLevels {
 // One 256-thread workgroup per 64 consecutive anchors of one level: their
 // (64 x cs) f32 head logits are one contiguous span, staged into LDS with
 // coalesced 16-B loads at a padded row stride (cs + 4 floats: rows 20 banks
-// apart, conflict-free fragment reads).  Four lanes share an anchor: lane
+// apart at 80 classes, conflict-free fragment reads).  cs is 4 REG + nc
+// rounded up to a multiple of 4: the (at most 3) padding logits of a row are
+// zeros, and nc stays exact in the class scan and in raw.  Four lanes share
+// an anchor: lane
 // part p takes the DFL side p (softmax expectation over REG bins) and the
 // classes p, p+4, ...; the quad then combines the four sides and the
 // first-max class with lane shuffles.
@@ -40,8 +43,12 @@ __device__ __forceinline__ float head_sigmoid(float x) {
 }
 
 // The fused head's MFMA section with compile-time trip counts (KB box /
-// KC class 32-channel k-steps, NCF class fragments: YOLOv8n's head is
-// KB = 2, KC = 3, NCF = 5): every A / B fragment load of the wave is issued
+// KC class 32-channel k-steps, NCF class fragments: YOLOv8n's 80-class head
+// is KB = 2, KC = 3, NCF = 5; with nc <= 64 classes its class branch is 64
+// wide: KC = 2, NCF = ceil(nc / 16) in 1..4, the last fragment's classes
+// beyond nc masked out of the scan; the packed weights and bias are padded to
+// 16 couts, so every fragment row exists): every A / B fragment load of the
+// wave is issued
 // before the first MFMA, so the wave waits out one L2 latency instead of
 // one per (fragment, k-step) -- the runtime-bound loops compiled to a
 // load / s_waitcnt vmcnt(0) / MFMA chain.  Same k order and sums as the
@@ -273,12 +280,15 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B,
             const f32x4 bb = *(const f32x4*)(L.b_cls + co);
             float* d = lg + (size_t)(wave * 16 + col) * (L.cs + 4) + 4 * REG + co;
             const f32x4 v = acc[m] + bb;
-            // the last fragment may run past nc: keep the padding out of the row
+            // the last fragment may run past nc: zeros in the row's padding
+            // (classes nc .. cs - 4 REG - 1, fewer than 4), nothing beyond the row
             if (co + 3 < nc) {
               *(f32x4*)d = v;
             } else {
+              const int ncp = L.cs - 4 * REG;
+#pragma unroll
               for (int i = 0; i < 4; ++i)
-                if (co + i < nc) d[i] = v[i];
+                if (co + i < ncp) d[i] = co + i < nc ? v[i] : 0.f;
             }
           }
         }
@@ -433,7 +443,8 @@ int decode_segments(const HeadLevel* lv, int nlv) {
 }
 
 int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_max, float conf,
-                         float* raw, Cand* cand, int cand_cap, int* cand_n, hipStream_t s) {
+                         float* raw, Cand* cand, int cand_cap, int* cand_n, hipStream_t s,
+                         int* form) {
   if (nlv < 1 || nlv > 4 || reg_max != 16) {
     set_error("detect decode: nlv=%d reg_max=%d unsupported", nlv, reg_max);
     return RV_EINVAL;
@@ -452,14 +463,24 @@ int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_ma
       return RV_EINVAL;
     }
   }
+  // the rows hold 4 * reg_max + nc logits (then padding): every class read
+  // stays inside the row and the (64 x cs) tile inside 64 KB of LDS
+  if (nc < 1 || nc > 128 || cs < 4 * reg_max + nc) {
+    set_error("detect decode: nc=%d outside 1..128 or beyond the logits row (cs %d)", nc, cs);
+    return RV_EINVAL;
+  }
   const size_t smem = (size_t)64 * (cs + 4) * 4;
   const bool fused = lv[0].feat != nullptr;
   // YOLOv8n's fused head (every level: box 64 -> 64, class 80 -> 80): the
   // compile-time MFMA section
   // (it keeps the class scores in registers: no raw output, no logits copy)
-  bool fixed = fused && nc == 80 && raw == nullptr;
+  // -- and the same head with at most 64 classes (class 64 -> nc: two class
+  // k-steps, ceil(nc / 16) <= 4 class fragments)
+  const int cin_c_fixed = nc == 80 ? 80 : 64;
+  bool fixed = fused && (nc == 80 || nc <= 64) && raw == nullptr;
   for (int i = 0; i < nlv && fixed; ++i)
-    fixed = lv[i].cin_b == 64 && lv[i].cin_c == 80 && lv[i].logits_out == nullptr;
+    fixed = lv[i].cin_b == 64 && lv[i].cin_c == cin_c_fixed && lv[i].logits_out == nullptr;
+  if (form) *form = !fused ? 0 : (fixed ? 2 : 1);
   if (smem > 64 * 1024) {  // only raise the cap when the head needs it (large nc)
     // best effort: a failure surfaces as the launch error reported below
     (void)hipFuncSetAttribute(fused ? (const void*)detect_decode_kernel<16, true>
@@ -474,7 +495,8 @@ int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_ma
   }
   if (fused) {
     for (int i = 0; i < nlv; ++i)
-      if (lv[i].cs != 4 * reg_max + nc || lv[i].cin_b % 8 || lv[i].cin_c % 8 || lv[i].feat_cs % 8) {
+      if (lv[i].cs != ((4 * reg_max + nc + 3) & ~3) || lv[i].cin_b % 8 || lv[i].cin_c % 8 ||
+          lv[i].feat_cs % 8) {
         set_error("fused head: bad level %d geometry", i);
         return RV_EINVAL;
       }
@@ -482,8 +504,18 @@ int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_ma
       // anchor tiles per block: enough blocks to fill the chip several times
       int tpb = 4;
       while (tpb > 1 && (long)ceil_div(nblk, tpb) * B < 4L * num_cus()) --tpb;
-      detect_decode_kernel<16, true, 2, 3, 5, 80><<<dim3(ceil_div(nblk, tpb), B), 256, smem, s>>>(
-          h, B, nc, conf, raw, cand, cand_cap, cand_n, nblk, tpb);
+      const dim3 grid(ceil_div(nblk, tpb), B);
+#define RV_FIXED_HEAD(KC_, NCF_)                                                  \
+  detect_decode_kernel<16, true, 2, KC_, NCF_, 16 * NCF_><<<grid, 256, smem, s>>>( \
+      h, B, nc, conf, raw, cand, cand_cap, cand_n, nblk, tpb)
+      switch (nc == 80 ? 5 : ceil_div(nc, 16)) {
+        case 5: RV_FIXED_HEAD(3, 5); break;
+        case 4: RV_FIXED_HEAD(2, 4); break;
+        case 3: RV_FIXED_HEAD(2, 3); break;
+        case 2: RV_FIXED_HEAD(2, 2); break;
+        default: RV_FIXED_HEAD(2, 1); break;
+      }
+#undef RV_FIXED_HEAD
     } else {
       detect_decode_kernel<16, true><<<dim3(nblk, B), 256, smem, s>>>(h, B, nc, conf, raw, cand,
                                                                       cand_cap, cand_n, nblk, 1);

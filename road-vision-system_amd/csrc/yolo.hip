@@ -43,9 +43,11 @@ static void plan(Model& M) {
   M.X21 = M.newbuf("X21", 5, v.h21);
   for (int i = 0; i < 3; ++i) {
     const std::string l = std::to_string(i);
-    M.DA[i] = M.newbuf("DA" + l, 3 + i, v.c2d + v.c3d);
-    M.DB[i] = M.newbuf("DB" + l, 3 + i, v.c2d + v.c3d, false, true);  // bf16: the decode's features
-    M.HD[i] = M.newbuf("HD" + l, 3 + i, 4 * v.reg + v.nc, true);
+    // class branch c3p wide, logits rows hcs floats: the padding channels
+    // (none in the 80-class plans) hold exact zeros
+    M.DA[i] = M.newbuf("DA" + l, 3 + i, v.c2d + v.c3p);
+    M.DB[i] = M.newbuf("DB" + l, 3 + i, v.c2d + v.c3p, false, true);  // bf16: the decode's features
+    M.HD[i] = M.newbuf("HD" + l, 3 + i, v.hcs, true);
   }
   // one temp per bottleneck (its first conv's output), named "prefix.m.i":
   // no buffer is ever overwritten inside a forward, so every layer stays
@@ -138,10 +140,10 @@ struct Exec {
     a.in_co = in.co;
     a.Hin = M->map_h[io.li];
     a.Win = M->map_w[io.li];
-    a.Cin = c.cin;
+    a.Cin = c.pcin;
     a.w = wptr(c);
     a.bias = bptr(c);
-    a.Cout = c.cout;
+    a.Cout = c.pcout;
     a.k = c.k;
     a.stride = c.s;
     a.pad = c.k / 2;
@@ -277,10 +279,10 @@ struct Exec {
     ConvArgs a = args(c1, io1);
     trace(c1, io1);
     trace(c2, io2);
-    a.Cout = c1.cout + c2.cout;
-    a.g2_cout0 = c1.cout;
+    a.Cout = c1.pcout + c2.pcout;
+    a.g2_cout0 = c1.pcout;
     a.g2_in_co = in2.co;
-    a.g2_Cin = c2.cin;
+    a.g2_Cin = c2.pcin;
     a.g2_w = wptr(c2);
     a.g2_bias = bptr(c2);
     a.g2_wscale = wsptr(c2);
@@ -523,8 +525,8 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
   // queues -- r04: +3 % in the pipeline with the heads on the caller's
   // stream) keeps everything on the caller's stream.
   const View P[3] = {View{M->X15, v.h15, 0}, View{M->X18, v.h18, 0}, View{M->X21, v.h21, 0}};
-  const int dcs = v.c2d + v.c3d, hcs = 4 * v.reg + v.nc;
-  const bool fuse_head = v.c2d % 8 == 0 && v.c3d % 8 == 0;
+  const int dcs = v.c2d + v.c3p, hcs = v.hcs;
+  const bool fuse_head = v.c2d % 8 == 0 && v.c3p % 8 == 0;
   // profiled forwards time every launch alone (per-launch roofline), so the
   // heads stay on the caller's stream there; so do batches under 8, whose
   // few-us head launches gain less from the overlap than the fork / join
@@ -558,8 +560,8 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
     E.trace(sc, {fc, 3 + i, View{M->HD[i], hcs, 4 * v.reg}});
     L.feat = (const bf16_t*)E.ptr(M->DB[i]);
     L.feat_cs = dcs;
-    L.cin_b = sa.cin;
-    L.cin_c = sc.cin;
+    L.cin_b = sa.pcin;
+    L.cin_c = sc.pcin;
     L.w_box = E.wptr(sa);
     L.w_cls = E.wptr(sc);
     L.b_box = E.bptr(sa);
@@ -592,7 +594,7 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
   if (E.status) return E.status;
   if (M->prof.active()) M->prof.n_fwd++;
   return launch_detect_decode(hl, 3, B, v.nc, v.reg, conf, raw_out, (Cand*)cand, cand_cap, cand_n,
-                              E.s);
+                              E.s, &M->head_form);
 }
 
 // Part 4 must continue the handle's last part 3, part 2 its last part 0 / 1 / 4:
@@ -619,11 +621,17 @@ extern "C" int rv_yolo_create(int variant, const void* dev_packed, int max_B, in
 
 extern "C" int rv_yolo_create2(int variant, int dtype, const void* dev_packed, int max_B, int in_h,
                                int in_w, void** handle) {
+  return rv_yolo_create3(variant, dtype, 80, dev_packed, max_B, in_h, in_w, handle);
+}
+
+extern "C" int rv_yolo_create3(int variant, int dtype, int nc, const void* dev_packed, int max_B,
+                               int in_h, int in_w, void** handle) {
   RV_CHECK_ARG(handle && dev_packed, "null pointer");
+  if (const int st = check_plan_args(variant, dtype, nc)) return st;
   RV_CHECK_ARG(max_B > 0 && in_h > 0 && in_w > 0 && in_h % 32 == 0 && in_w % 32 == 0,
                "input %dx%d must be positive multiples of 32", in_h, in_w);
   Model* M = new Model();
-  if (!build_def(variant, M->def, dtype)) {
+  if (!build_def(variant, M->def, dtype, nc)) {
     delete M;
     set_error("unknown variant %d / dtype %d", variant, dtype);
     return RV_EINVAL;
@@ -719,6 +727,10 @@ extern "C" size_t rv_yolo_ws_bytes(void* h, int B) {
 }
 
 extern "C" int rv_yolo_num_anchors(void* h) { return h ? ((Model*)h)->nA : 0; }
+
+extern "C" int rv_yolo_num_classes(void* h) { return h ? ((Model*)h)->def.v.nc : 0; }
+
+extern "C" int rv_yolo_head_form(void* h) { return h ? ((Model*)h)->head_form : RV_EINVAL; }
 
 extern "C" int rv_yolo_cand_segments(void* h) {
   if (!h) return 0;

@@ -14,15 +14,25 @@ struct ConvSpec {
   size_t w_off = 0, b_off = 0;  // byte offsets in the packed blob
   size_t ws_off = 0;            // fp8 convs: per-cout weight scales (f32)
   bool f8 = false;              // fp8 weights / inputs (RV_YOLO_DTYPE_FP8 plans)
+  // widths the plan launches the conv with: cin / cout, but for the Detect
+  // class branch of a plan whose c3d is no multiple of 8 (Variant::c3p).  The
+  // packed rows / columns beyond cout / cin are zero, so the extra channels
+  // are exact zeros and every logical channel keeps its sums.
+  int pcin = 0, pcout = 0;
 };
 
 struct Variant {
   int c1, c2, c3, c4, c5;   // backbone widths (P1..P5)
   int h12, h15, h18, h21;   // head widths
   int nb, nm;               // C2f repeats for "3" and "6"
-  int c2d, c3d;             // Detect branch widths
+  int c2d, c3d;             // Detect branch widths (the Ultralytics ones)
   int nc = 80, reg = 16;
+  int c3p;                  // c3d as the plan runs it: padded to a multiple of 8
+  int hcs;                  // f32 logits row stride: 4 * reg + nc padded to a multiple of 4
 };
+
+// class counts a plan supports: the NMS class mask is 4 x 32 bits wide
+constexpr int kMinClasses = 1, kMaxClasses = 128;
 
 struct ModelDef {
   Variant v;
@@ -34,6 +44,8 @@ struct ModelDef {
   size_t q_off = 0, q_bytes = 0;
   int add(const std::string& n, int ci, int co, int k, int s, int act = 1) {
     convs.push_back(ConvSpec{n, ci, co, k, s, act});
+    convs.back().pcin = ci;
+    convs.back().pcout = co;
     return (int)convs.size() - 1;
   }
   void c2f(const std::string& p, int c1, int c2, int n) {
@@ -52,7 +64,11 @@ struct ModelDef {
   }
 };
 
-bool build_def(int variant, ModelDef& m, int dtype = RV_YOLO_DTYPE_BF16);
+// false: unknown variant / dtype, or nc outside [kMinClasses, kMaxClasses]
+bool build_def(int variant, ModelDef& m, int dtype = RV_YOLO_DTYPE_BF16, int nc = 80);
+// RV_OK, or RV_EINVAL with rv_last_error naming what is wrong with
+// (variant, dtype, nc): the range of nc, fp8 with nc != 80
+int check_plan_args(int variant, int dtype, int nc);
 size_t packed_bytes(const ModelDef& m);
 size_t flat_floats(const ModelDef& m);
 

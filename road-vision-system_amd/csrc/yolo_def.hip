@@ -32,12 +32,27 @@ static bool variant_widths(int variant, Variant& v) {
   v.nm = rep(6);
   v.c2d = std::max(std::max(16, v.h15 / 4), v.reg * 4);
   v.c3d = std::max(v.h15, std::min(v.nc, 100));
+  v.c3p = (v.c3d + 7) & ~7;
+  v.hcs = (4 * v.reg + v.nc + 3) & ~3;
   return true;
 }
 
 static size_t conv0q_bytes(int C0) { return 3 * (size_t)C0 * 64 + 20 * (size_t)C0; }
 
-bool build_def(int variant, ModelDef& m, int dtype) {
+int check_plan_args(int variant, int dtype, int nc) {
+  RV_CHECK_ARG(variant >= 0 && variant <= 4, "unknown variant %d", variant);
+  RV_CHECK_ARG(dtype == RV_YOLO_DTYPE_BF16 || dtype == RV_YOLO_DTYPE_FP8, "unknown dtype %d", dtype);
+  RV_CHECK_ARG(nc >= kMinClasses && nc <= kMaxClasses, "nc = %d outside the supported range %d..%d",
+               nc, kMinClasses, kMaxClasses);
+  RV_CHECK_ARG(dtype != RV_YOLO_DTYPE_FP8 || nc == 80,
+               "fp8 plans support nc = 80 only (got nc = %d): the fp8 parity rests on the 80-class "
+               "calibration; use the bf16 plan", nc);
+  return RV_OK;
+}
+
+bool build_def(int variant, ModelDef& m, int dtype, int nc) {
+  if (nc < kMinClasses || nc > kMaxClasses) return false;
+  m.v.nc = nc;
   if (!variant_widths(variant, m.v)) return false;
   if (dtype != RV_YOLO_DTYPE_BF16 && dtype != RV_YOLO_DTYPE_FP8) return false;
   m.dtype = dtype;
@@ -68,9 +83,12 @@ bool build_def(int variant, ModelDef& m, int dtype) {
   }
   for (int i = 0; i < 3; ++i) {
     const std::string p = "model.22.cv3." + std::to_string(i);
-    m.add(p + ".0", chs[i], v.c3d, 3, 1);
-    m.add(p + ".1", v.c3d, v.c3d, 3, 1);
-    m.add(p + ".2", v.c3d, v.nc, 1, 1, 0);
+    // the plan runs the branch c3p wide (c3d padded to 8: 16-byte feature
+    // rows); the state_dict shapes and the packed layout keep c3d
+    m.convs[m.add(p + ".0", chs[i], v.c3d, 3, 1)].pcout = v.c3p;
+    ConvSpec& c1 = m.convs[m.add(p + ".1", v.c3d, v.c3d, 3, 1)];
+    c1.pcin = c1.pcout = v.c3p;
+    m.convs[m.add(p + ".2", v.c3d, v.nc, 1, 1, 0)].pcin = v.c3p;
   }
   // packed layout: conv 0 keeps f32 OIHW (VALU conv), the rest bf16
   // [Cout_pad16][ky][kx][Cin_pad32]; biases f32 [Cout_pad16]; 256-B aligned.
@@ -189,15 +207,24 @@ static uint16_t host_f2bf(float f) {
 
 using namespace rv;
 
-extern "C" int rv_yolo_num_convs(int variant) {
+extern "C" int rv_yolo_num_convs(int variant) { return rv_yolo_num_convs_nc(variant, 80); }
+
+extern "C" int rv_yolo_num_convs_nc(int variant, int nc) {
+  if (const int st = check_plan_args(variant, RV_YOLO_DTYPE_BF16, nc)) return st;
   ModelDef m;
-  if (!build_def(variant, m)) return RV_EINVAL;
+  if (!build_def(variant, m, RV_YOLO_DTYPE_BF16, nc)) return RV_EINVAL;
   return (int)m.convs.size();
 }
 
 extern "C" int rv_yolo_conv_info(int variant, int idx, int* info, char* name, int name_cap) {
+  return rv_yolo_conv_info_nc(variant, 80, idx, info, name, name_cap);
+}
+
+extern "C" int rv_yolo_conv_info_nc(int variant, int nc, int idx, int* info, char* name,
+                                    int name_cap) {
+  if (const int st = check_plan_args(variant, RV_YOLO_DTYPE_BF16, nc)) return st;
   ModelDef m;
-  RV_CHECK_ARG(build_def(variant, m), "unknown variant %d", variant);
+  RV_CHECK_ARG(build_def(variant, m, RV_YOLO_DTYPE_BF16, nc), "unknown variant %d", variant);
   RV_CHECK_ARG(idx >= 0 && idx < (int)m.convs.size() && info, "bad conv index %d", idx);
   const ConvSpec& c = m.convs[idx];
   info[0] = c.cin;
@@ -212,15 +239,25 @@ extern "C" int rv_yolo_conv_info(int variant, int idx, int* info, char* name, in
   return RV_OK;
 }
 
-extern "C" size_t rv_yolo_flat_floats(int variant) {
+extern "C" size_t rv_yolo_flat_floats(int variant) { return rv_yolo_flat_floats_nc(variant, 80); }
+
+extern "C" size_t rv_yolo_flat_floats_nc(int variant, int nc) {
   ModelDef m;
-  if (!build_def(variant, m)) return 0;
+  if (check_plan_args(variant, RV_YOLO_DTYPE_BF16, nc) ||
+      !build_def(variant, m, RV_YOLO_DTYPE_BF16, nc))
+    return 0;
   return flat_floats(m);
 }
 
 extern "C" size_t rv_yolo_packed_bytes2(int variant, int dtype) {
   ModelDef m;
   if (!build_def(variant, m, dtype)) return 0;
+  return packed_bytes(m);
+}
+
+extern "C" size_t rv_yolo_packed_bytes3(int variant, int dtype, int nc) {
+  ModelDef m;
+  if (check_plan_args(variant, dtype, nc) || !build_def(variant, m, dtype, nc)) return 0;
   return packed_bytes(m);
 }
 
@@ -237,10 +274,17 @@ extern "C" int rv_yolo_pack(int variant, const float* flat, size_t n, void* host
 
 extern "C" int rv_yolo_pack2(int variant, int dtype, const float* flat, size_t n, void* host_out,
                              size_t out_bytes) {
+  return rv_yolo_pack3(variant, dtype, 80, flat, n, host_out, out_bytes);
+}
+
+extern "C" int rv_yolo_pack3(int variant, int dtype, int nc, const float* flat, size_t n,
+                             void* host_out, size_t out_bytes) {
+  if (const int st = check_plan_args(variant, dtype, nc)) return st;
   ModelDef m;
-  RV_CHECK_ARG(build_def(variant, m, dtype), "unknown variant %d / dtype %d", variant, dtype);
+  RV_CHECK_ARG(build_def(variant, m, dtype, nc), "unknown variant %d / dtype %d", variant, dtype);
   RV_CHECK_ARG(flat && host_out, "null pointer");
-  RV_CHECK_ARG(n == flat_floats(m), "flat weights: got %zu floats, need %zu", n, flat_floats(m));
+  RV_CHECK_ARG(n == flat_floats(m), "flat weights: got %zu floats, need %zu (variant %d, nc %d)", n,
+               flat_floats(m), variant, nc);
   RV_CHECK_ARG(out_bytes >= packed_bytes(m), "packed buffer too small");
   uint8_t* out = (uint8_t*)host_out;
   memset(out, 0, packed_bytes(m));

@@ -138,6 +138,10 @@ struct Model {
   int head_streams = 1;            // RV_YOLO_OPT_HEAD_STREAMS
   int fuse_cv1 = 1;                // RV_YOLO_OPT_FUSE_CV1
   int c2f_tap_pairs = 1;           // RV_YOLO_OPT_C2F_TAP_PAIRS
+  // decode form of the last forward that reached the decode (rv_yolo_head_form;
+  // -1 before one): 0 unfused last stage, 1 fused + LDS class scan, 2 fused
+  // with register-resident class scores
+  int head_form = -1;
   std::vector<Buf> bufs;
   int nA = 0;
   int map_h[6], map_w[6];  // stride 2^i maps

@@ -105,6 +105,16 @@ _SIGS = {
     "rv_yolo_packed_bytes2": (c_size_t, [c_int, c_int]),
     "rv_yolo_pack2": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t]),
     "rv_yolo_create2": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, POINTER(c_void_p)]),
+    # custom class counts (nc 1..128)
+    "rv_yolo_num_convs_nc": (c_int, [c_int, c_int]),
+    "rv_yolo_conv_info_nc": (c_int, [c_int, c_int, c_int, POINTER(c_int), ctypes.c_char_p, c_int]),
+    "rv_yolo_flat_floats_nc": (c_size_t, [c_int, c_int]),
+    "rv_yolo_packed_bytes3": (c_size_t, [c_int, c_int, c_int]),
+    "rv_yolo_pack3": (c_int, [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t]),
+    "rv_yolo_create3": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                POINTER(c_void_p)]),
+    "rv_yolo_num_classes": (c_int, [c_void_p]),
+    "rv_yolo_head_form": (c_int, [c_void_p]),
     "rv_yolo_set_act_scales": (c_int, [c_void_p, c_void_p, c_int]),
     "rv_yolo_buffer_esize": (c_int, [c_void_p, c_int]),
     "rv_yolo_buffer_name": (c_int, [c_void_p, c_int, ctypes.c_char_p, c_int]),
@@ -207,7 +217,8 @@ _RECORDABLE = {"rv_clahe_median_letterbox_u8", "rv_clahe_median_u8", "rv_letterb
 
 _NOCHECK = {"rv_preprocess_chain_route", "rv_sched_num_nodes", "rv_sched_event_query", "rv_abi_version", "rv_cand_segments", "rv_yolo_cand_segments", "rv_clahe_median_fits", "rv_clahe_median_letterbox_fits", "rv_yolo_num_convs", "rv_yolo_num_anchors",
             "rv_yolo_num_buffers", "rv_yolo_trace", "rv_yolo_profile_read", "rv_yolo_tuned_config",
-            "rv_yolo_profile_bytes", "rv_yolo_profile_times", "rv_yolo_buffer_esize", "rv_yolo_conv_candidates"}
+            "rv_yolo_profile_bytes", "rv_yolo_profile_times", "rv_yolo_buffer_esize", "rv_yolo_conv_candidates",
+            "rv_yolo_num_classes", "rv_yolo_head_form"}
 
 
 _recorder = None  # a schedule.Schedule while one is being recorded

@@ -20,6 +20,12 @@ src/detect/yolo_ultralytics.py:16-17):
   * the plan's own names (``model.2.m.0.cv1.weight / .bias``, round-1 files).
 The DFL conv (``model.22.dfl.conv.weight``, a fixed arange) and
 ``num_batches_tracked`` are ignored.
+
+The class count is the checkpoint's own (the first dimension of
+``model.22.cv3.0.2.weight``, 1..128), as the reference's YOLO(cfg["model"])
+takes it from the checkpoint; ``detect.nc`` may state it and must then agree,
+``detect.names`` names the classes (names_from_config).  Synthetic weights
+exist for 80 classes only.
 """
 from __future__ import annotations
 
@@ -54,14 +60,23 @@ def variant_of(model_name: str) -> int:
     raise ValueError(f"unsupported model '{model_name}' (YOLOv8 n/s/m/l/x only)")
 
 
-def conv_list(variant: int) -> List[Tuple[str, int, int, int, int, int]]:
-    """[(name, cin, cout, k, stride, silu)] in packing order."""
+NC_MIN, NC_MAX = 1, 128  # class counts the native plan supports (include/rvhip.h)
+CLS_KEY = "model.22.cv3.0.2.weight"  # its first dimension is the checkpoint's class count
+
+
+def conv_list(variant: int, nc: int = 80) -> List[Tuple[str, int, int, int, int, int]]:
+    """[(name, cin, cout, k, stride, silu)] in packing order: the Ultralytics
+    state_dict shapes of a YOLOv8 with `nc` classes."""
     lib = _lib.load()
     out = []
     info = (ctypes.c_int * 5)()
     name = ctypes.create_string_buffer(96)
-    for i in range(lib.rv_yolo_num_convs(variant)):
-        _lib.check(lib.rv_yolo_conv_info(variant, i, info, name, 96), "rv_yolo_conv_info")
+    n = lib.rv_yolo_num_convs_nc(variant, int(nc))
+    if n < 0:
+        _lib.check(n, "rv_yolo_num_convs_nc")
+    for i in range(n):
+        _lib.check(lib.rv_yolo_conv_info_nc(variant, int(nc), i, info, name, 96),
+                   "rv_yolo_conv_info_nc")
         out.append((name.value.decode(), info[0], info[1], info[2], info[3], info[4]))
     return out
 
@@ -100,8 +115,9 @@ def base_weights(rng, seed: int, idx: int, cin: int, cout: int, k: int, smooth: 
     return w, b
 
 
-def synthetic_weights(variant: int, seed: int = 0) -> np.ndarray:
-    """Seeded BN-fused-like weights as one flat f32 array.
+def synthetic_weights(variant: int, seed: int = 0, nc: int = 80) -> np.ndarray:
+    """Seeded BN-fused-like weights as one flat f32 array (80 classes only:
+    the shipped calibration is the 80-class one).
 
     Base weights (base_weights: He-normal, for some variants mixed with a
     smooth part, data/synthetic_calib.npz "<variant>/smooth"), then the
@@ -110,6 +126,10 @@ def synthetic_weights(variant: int, seed: int = 0) -> np.ndarray:
     tests/golden/make_yolo_scales.py), so every conv's pre-activation is O(1)
     like a trained model's fused BN output and a road frame yields a few
     hundred NMS candidates."""
+    if int(nc) != 80:
+        raise ValueError(f"no synthetic calibration for nc = {nc} in {os.path.basename(_CALIB)} "
+                         "(the shipped calibration is 80-class); a model with a custom class "
+                         "count needs a detect.weights file (a local state_dict)")
     rng = np.random.default_rng(seed)
     parts = []
     with np.load(_CALIB, allow_pickle=False) as cal:
@@ -174,71 +194,142 @@ def _strip_prefix(t: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     return t
 
 
-def flat_from_state_dict(tensors: Dict[str, np.ndarray], variant: int) -> np.ndarray:
-    """Flat f32 weights (the plan's conv order) from an Ultralytics
-    DetectionModel state_dict, fused or not (see the module docstring)."""
+def nc_of_state_dict(tensors: Dict[str, np.ndarray]) -> int:
+    """The class count of an Ultralytics DetectionModel state_dict: the first
+    dimension of model.22.cv3.0.2.weight (a plain nn.Conv2d, so the key is the
+    same before and after model.fuse(), with or without the "model." nesting)."""
     t = _strip_prefix(tensors)
+    if CLS_KEY not in t:
+        raise KeyError(f"{CLS_KEY}: not in the state_dict (the class count is read from it)")
+    nc = int(np.asarray(t[CLS_KEY]).shape[0])
+    if not NC_MIN <= nc <= NC_MAX:
+        raise ValueError(f"{CLS_KEY} has {nc} classes: outside the supported range "
+                         f"{NC_MIN}..{NC_MAX}")
+    return nc
+
+
+def _shaped(t: Dict[str, np.ndarray], key: str, shape, variant: int, nc: int) -> np.ndarray:
+    a = np.asarray(t[key], np.float32)
+    if a.size != int(np.prod(shape)):
+        raise ValueError(f"{key}: shape {tuple(a.shape)} does not fit YOLOv8 variant {variant} "
+                         f"with nc = {nc} (expected {tuple(shape)})")
+    return a.reshape(shape)
+
+
+def flat_from_state_dict(tensors: Dict[str, np.ndarray], variant: int, nc: int = None,
+                         return_nc: bool = False):
+    """Flat f32 weights (the plan's conv order) from an Ultralytics
+    DetectionModel state_dict, fused or not (see the module docstring).  The
+    class count is the checkpoint's own (nc_of_state_dict); an `nc` that
+    disagrees with it is an error.  return_nc: (flat, nc) instead of flat."""
+    t = _strip_prefix(tensors)
+    have = nc_of_state_dict(t)
+    if nc is not None and int(nc) != have:
+        raise ValueError(f"detect.nc = {int(nc)} but the checkpoint has {have} classes "
+                         f"({CLS_KEY} has {have} rows)")
+    nc = have
     parts = []
-    for name, cin, cout, k, s, act in conv_list(variant):
+    for name, cin, cout, k, s, act in conv_list(variant, nc):
         shape = (cout, cin, k, k)
         if name + ".conv.weight" in t:  # Conv block (conv + bn + SiLU)
-            w = np.asarray(t[name + ".conv.weight"], np.float32).reshape(shape)
+            w = _shaped(t, name + ".conv.weight", shape, variant, nc)
             if name + ".bn.running_var" in t:
                 w, b = fold_bn(w, t[name + ".bn.weight"], t[name + ".bn.bias"],
                                t[name + ".bn.running_mean"], t[name + ".bn.running_var"],
                                t.get(name + ".conv.bias"))
             elif name + ".conv.bias" in t:
-                b = np.asarray(t[name + ".conv.bias"], np.float32)
+                b = _shaped(t, name + ".conv.bias", (cout,), variant, nc)
             else:
                 raise KeyError(f"{name}: neither .bn.* nor .conv.bias in the state_dict")
         elif name + ".weight" in t:  # Detect's plain nn.Conv2d / the plan's own names
-            w = np.asarray(t[name + ".weight"], np.float32).reshape(shape)
-            b = np.asarray(t[name + ".bias"], np.float32)
+            w = _shaped(t, name + ".weight", shape, variant, nc)
+            b = _shaped(t, name + ".bias", (cout,), variant, nc)
         else:
             raise KeyError(f"{name}: no weights in the state_dict "
                            f"(expected {name}.conv.weight or {name}.weight)")
         parts += [w.ravel(), b.reshape(cout)]
-    return np.concatenate(parts).astype(np.float32)
+    flat = np.concatenate(parts).astype(np.float32)
+    return (flat, nc) if return_nc else flat
 
 
-def load_weights(path: str, variant: int) -> np.ndarray:
+def load_weights(path: str, variant: int, nc: int = None, return_nc: bool = False):
     """Flat f32 array from a local Ultralytics checkpoint (state_dict keys,
-    fused or unfused; see read_state_dict for the accepted formats)."""
-    return flat_from_state_dict(read_state_dict(path), variant)
+    fused or unfused; see read_state_dict for the accepted formats), with the
+    checkpoint's own class count (flat_from_state_dict: `nc`, `return_nc`)."""
+    return flat_from_state_dict(read_state_dict(path), variant, nc, return_nc)
 
 
 DTYPES = {"bf16": 0, "fp8": 1}  # RV_YOLO_DTYPE_BF16 / RV_YOLO_DTYPE_FP8
 
 
-def pack(variant: int, flat: np.ndarray, dtype: str = "bf16") -> np.ndarray:
+def check_fp8_nc(dtype: str, nc: int) -> None:
+    if dtype == "fp8" and int(nc) != 80:
+        raise ValueError(f"dtype 'fp8' supports nc = 80 only (got nc = {int(nc)}): the fp8 parity "
+                         "rests on the 80-class calibration; run a custom class count in bf16")
+
+
+def pack(variant: int, flat: np.ndarray, dtype: str = "bf16", nc: int = 80) -> np.ndarray:
     """Device layout as a u8 host array: bf16 [Cout16][ky][kx][Cin32] + f32
-    bias, or (dtype 'fp8') OCP e4m3 [Cout16][ky][kx][Cin64] + f32 bias + f32
-    per-cout power-of-two scales for every conv the fp8 plan runs in fp8."""
+    bias, or (dtype 'fp8', nc = 80 only) OCP e4m3 [Cout16][ky][kx][Cin64] +
+    f32 bias + f32 per-cout power-of-two scales for every conv the fp8 plan
+    runs in fp8.  `flat` holds the state_dict shapes of conv_list(variant, nc)."""
     lib = _lib.load()
     dt = DTYPES[dtype]
+    check_fp8_nc(dtype, nc)
     flat = np.ascontiguousarray(flat, np.float32)
-    nbytes = lib.rv_yolo_packed_bytes2(variant, dt)
+    nbytes = lib.rv_yolo_packed_bytes3(variant, dt, int(nc))
     out = np.zeros(nbytes, np.uint8)
-    _lib.check(lib.rv_yolo_pack2(variant, dt, flat.ctypes.data, flat.size, out.ctypes.data, nbytes),
-               "rv_yolo_pack2")
+    _lib.check(lib.rv_yolo_pack3(variant, dt, int(nc), flat.ctypes.data, flat.size, out.ctypes.data,
+                                 nbytes), "rv_yolo_pack3")
     return out
 
 
-def weights_from_config(det_cfg: dict, variant: int) -> np.ndarray:
-    """The detector's weights for a detect config (default.yaml:38-45 keys):
-    ``weights: <path>`` loads a local Ultralytics state_dict (load_weights);
-    ``weights: synthetic`` opts in to the seeded synthetic weights (``seed``).
-    With no ``weights`` key the synthetic weights are used too, with a
-    warning: the reference's YOLO(model) loads the real checkpoint, and a
-    production run must not silently detect with random weights."""
+def detector_weights(det_cfg: dict, variant: int) -> Tuple[np.ndarray, int]:
+    """(flat weights, class count) for a detect config (default.yaml:38-45
+    keys plus ``nc``): ``weights: <path>`` loads a local Ultralytics
+    state_dict and takes the class count from it (load_weights; a ``nc`` key
+    that disagrees is an error); ``weights: synthetic`` opts in to the seeded
+    synthetic weights (``seed``; 80 classes only).  With no ``weights`` key
+    the synthetic weights are used too, with a warning: the reference's
+    YOLO(model) loads the real checkpoint, and a production run must not
+    silently detect with random weights."""
     import warnings
     w = det_cfg.get("weights")
     seed = int(det_cfg.get("seed", 0))
+    nc = det_cfg.get("nc")
     if w and str(w).lower() != "synthetic":
-        return load_weights(str(w), variant)
+        return load_weights(str(w), variant, nc, return_nc=True)
     if not w:
         warnings.warn(f"detect.model={det_cfg.get('model', 'yolov8n.pt')!r} but no detect.weights "
                       "file is configured: using seeded SYNTHETIC weights (set detect.weights to "
                       "a local state_dict, or to 'synthetic' to silence this)", RuntimeWarning,
-                      stacklevel=2)
-    return synthetic_weights(variant, seed=seed)
+                      stacklevel=3)
+    nc = 80 if nc is None else int(nc)
+    return synthetic_weights(variant, seed=seed, nc=nc), nc
+
+
+def weights_from_config(det_cfg: dict, variant: int) -> np.ndarray:
+    """The flat weights of detector_weights(det_cfg, variant)."""
+    return detector_weights(det_cfg, variant)[0]
+
+
+def names_from_config(det_cfg: dict, nc: int) -> List[str]:
+    """Class names of a detect config as a list indexed by class id:
+    ``names`` may be a list or an {id: name} mapping (Ultralytics' `names`;
+    ids the mapping leaves out read str(id)).  Without the key: COCO80 for an
+    80-class model, else no names -- Detection.cls_name is then str(id), the
+    reference's own fallback (yolo_ultralytics.py:51).  More names than
+    classes is an error."""
+    names = det_cfg.get("names")
+    if names is None:
+        return list(COCO80) if nc == 80 else []
+    if isinstance(names, dict):
+        ids = {int(k): str(v) for k, v in names.items()}
+        if ids and (min(ids) < 0 or max(ids) >= nc):
+            raise ValueError(f"detect.names has class id {max(ids) if max(ids) >= nc else min(ids)}"
+                             f" but the model has {nc} classes (ids 0..{nc - 1})")
+        return [ids.get(k, str(k)) for k in range(max(ids) + 1)] if ids else []
+    names = [str(x) for x in names]
+    if len(names) > nc:
+        raise ValueError(f"detect.names lists {len(names)} names but the model has {nc} classes")
+    return names

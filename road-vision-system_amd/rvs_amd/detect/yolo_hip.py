@@ -22,7 +22,8 @@ from .. import _lib, kernels
 from .._lib import call, ptr, stream_ptr
 from .base import Detector
 from .types import Detection
-from .weights import COCO80, DTYPES, pack, variant_of, weights_from_config
+from .weights import (COCO80, DTYPES, NC_MAX, NC_MIN, check_fp8_nc, detector_weights,
+                      names_from_config, pack, variant_of)
 
 CAND_BYTES = 32
 
@@ -64,18 +65,27 @@ class YoloEngine:
     (OCP e4m3 weights and activations, power-of-two scales; include/rvhip.h
     RV_YOLO_DTYPE_FP8).  Its per-buffer activation scales come from
     `act_scales` (a saved calibration) or from calibrate(); a forward before
-    either raises."""
+    either raises.
+
+    `nc`: the model's class count (1..128; `flat_weights` holds the
+    state_dict shapes of weights.conv_list(variant, nc)).  raw predictions
+    are (B, 4 + nc, A), candidate and detection classes are < nc, and
+    classes_keep ids >= nc never match.  fp8 plans exist for nc = 80 only."""
 
     def __init__(self, variant: int, flat_weights: np.ndarray, max_batch: int, frame_hw,
                  imgsz: int = 640, stride: int = 32, conf: float = 0.25, iou: float = 0.7,
                  max_det: int = 100, classes_keep: Sequence[int] = (), max_wh: float = 7680.0,
                  max_nms: int = 30000, device="cuda", lanes: int = 1, dtype: str = "bf16",
-                 act_scales: Optional[Sequence[float]] = None):
+                 act_scales: Optional[Sequence[float]] = None, nc: int = 80):
         self.device = torch.device(device)
         self.variant = variant
         if dtype not in DTYPES:
             raise ValueError(f"dtype {dtype!r}: expected one of {sorted(DTYPES)}")
         self.dtype = dtype
+        self.nc = int(nc)
+        if not NC_MIN <= self.nc <= NC_MAX:
+            raise ValueError(f"nc = {nc} outside the supported range {NC_MIN}..{NC_MAX}")
+        check_fp8_nc(dtype, self.nc)
         self.flat = flat_weights
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         self.max_batch = int(max_batch)
@@ -84,18 +94,17 @@ class YoloEngine:
         self.max_nms = int(max_nms)  # Ultralytics non_max_suppression default
         self.geo = kernels.letterbox_geometry(self.H, self.W, imgsz, stride)
         self.in_h, self.in_w = self.geo[0], self.geo[1]
-        self.packed = torch.from_numpy(pack(variant, flat_weights, dtype)).to(self.device)
+        self.packed = torch.from_numpy(pack(variant, flat_weights, dtype, self.nc)).to(self.device)
         self.lanes = max(1, int(lanes))
         self._hs = []
         for _ in range(self.lanes):
             h = ctypes.c_void_p()
-            call("rv_yolo_create2", variant, DTYPES[dtype], ptr(self.packed), self.max_batch,
-                 self.in_h, self.in_w, ctypes.byref(h))
+            call("rv_yolo_create3", variant, DTYPES[dtype], self.nc, ptr(self.packed),
+                 self.max_batch, self.in_h, self.in_w, ctypes.byref(h))
             self._hs.append(h)
         self._h = h = self._hs[0]
         lib = _lib.load()
         self.A = lib.rv_yolo_num_anchors(h)
-        self.nc = 80
         self.ws_bytes = lib.rv_yolo_ws_bytes(h, self.max_batch)
         dev = self.device
         self.wss = [torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
@@ -168,9 +177,9 @@ class YoloEngine:
         (224, 448]); installs and returns them."""
         lib = _lib.load()
         B = lb.shape[0]
-        packed = torch.from_numpy(pack(self.variant, self.flat, "bf16")).to(self.device)
+        packed = torch.from_numpy(pack(self.variant, self.flat, "bf16", self.nc)).to(self.device)
         h = ctypes.c_void_p()
-        call("rv_yolo_create2", self.variant, 0, ptr(packed), B, self.in_h, self.in_w,
+        call("rv_yolo_create3", self.variant, 0, self.nc, ptr(packed), B, self.in_h, self.in_w,
              ctypes.byref(h))
         try:
             ws = torch.empty(lib.rv_yolo_ws_bytes(h, B), dtype=torch.uint8, device=self.device)
@@ -242,6 +251,13 @@ class YoloEngine:
         hidden-width-16 chains only (default), 2 = widths 16 and 32,
         False / 0 = none."""
         self._set_option(OPT_FUSE_C2F, 1 if on is True else (0 if on is False else int(on)))
+
+    def head_form(self, lane: int = 0) -> int:
+        """Decode form of forward context `lane`'s last forward
+        (rv_yolo_head_form): 0 unfused last head stage, 1 fused with the LDS
+        class scan, 2 fused with register-resident class scores; -1 before
+        any forward."""
+        return int(_lib.load().rv_yolo_head_form(self._hs[lane]))
 
     def letterbox(self, frames: torch.Tensor, slot: int = 0, off: int = 0) -> torch.Tensor:
         """Letterbox into images [off, off + B) of letterbox slot `slot`."""
@@ -373,13 +389,13 @@ class YOLOHip(Detector):
         if not torch.cuda.is_available():
             raise RuntimeError("YOLOHip needs an MI355X (HIP device); there is no CPU fallback")
         self.variant = variant_of(cfg.get("model", "yolov8n.pt"))
-        self.flat = weights_from_config(cfg, self.variant)
+        self.flat, self.nc = detector_weights(cfg, self.variant)
         self.conf = float(cfg.get("conf_thres", 0.25))
         self.iou = float(cfg.get("iou_thres", 0.7))
         self.max_det = int(cfg.get("max_det", 100))
         self.keep = [int(x) for x in cfg.get("classes_keep", [])]
         self.imgsz = int(cfg.get("imgsz", 640))
-        self.names = COCO80
+        self.names = names_from_config(cfg, self.nc)
         self._engines: Dict = {}
 
     def engine(self, H: int, W: int, max_batch: int = 1) -> YoloEngine:
@@ -390,7 +406,7 @@ class YOLOHip(Detector):
                 e.close()
             e = YoloEngine(self.variant, self.flat, max_batch, (H, W), imgsz=self.imgsz,
                            conf=self.conf, iou=self.iou, max_det=self.max_det,
-                           classes_keep=self.keep, device=self.device)
+                           classes_keep=self.keep, device=self.device, nc=self.nc)
             self._engines[key] = e
         return e
 

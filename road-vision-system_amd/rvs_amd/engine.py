@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from .config import load_config
 from .detect.types import Detection
-from .detect.weights import COCO80, variant_of, weights_from_config
+from .detect.weights import detector_weights, names_from_config, variant_of
 from .detect.yolo_hip import YoloEngine
 from .geometry import GroundProjector, build_projector
 from .handback import Record, handback
@@ -54,9 +54,12 @@ class RoadVisionEngine:
         self.tracking_enabled = bool(trk_cfg.get("enabled", False))
         self.variant = variant_of(det_cfg.get("model", "yolov8n.pt"))
         self.detector = None
+        # class count and names: the checkpoint's / the config's (detect.nc,
+        # detect.names); caller-supplied flat weights carry detect.nc classes
+        self.nc = int(det_cfg.get("nc", 80))
         if self.detect_enabled:
             if weights is None:
-                weights = weights_from_config(det_cfg, self.variant)
+                weights, self.nc = detector_weights(det_cfg, self.variant)
             self.detector = YoloEngine(
                 self.variant, weights, self.S * self.pair, (self.H, self.W),
                 imgsz=int(det_cfg.get("imgsz", 640)),
@@ -64,7 +67,7 @@ class RoadVisionEngine:
                 iou=float(det_cfg.get("iou_thres", 0.7)),
                 max_det=int(det_cfg.get("max_det", 100)),
                 classes_keep=[int(x) for x in det_cfg.get("classes_keep", [])],
-                device=self.device, lanes=lanes)
+                device=self.device, lanes=lanes, nc=self.nc)
             if self.detector.lanes > 1:
                 # a multi-lane engine runs pipelined stages (schedule.PipelinedRun):
                 # its forwards keep the Detect heads on the stage's own stream
@@ -99,7 +102,7 @@ class RoadVisionEngine:
             # each detection gets projector.distance_for_bbox when a projector exists
             self._untracked = _UntrackedMetrics(self.S, self.max_det, projector, self.device)
         self.proc = torch.empty((self.S, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
-        self.names = COCO80
+        self.names = names_from_config(det_cfg, self.nc)
         # result hand-back: device staging buffer + the pinned host record of step()
         self.record = Record(self.S, self.max_det, self.device)
         self.rec_stage = torch.empty(self.record.nbytes, dtype=torch.uint8, device=self.device)
