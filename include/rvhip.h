@@ -502,6 +502,38 @@ int rv_sort_stats(const void* state, int S, int* T_out, int* next_id_out, int* o
 int rv_sort_export(const void* state, int S, int tmax, double* x_out, int* meta, int* T_out,
                    void* stream);
 
+/* --- Per-camera ground projectors.  The reference runs one process per camera,
+ * each with its own geometry.projector, and SortTracker.update takes the
+ * projector per call (sort_tracker.py:212-278); the entries above project
+ * every stream of a batch with one host-side calibration.  The _cams entries
+ * read a table in DEVICE memory instead, one entry per stream (stream s uses
+ * cams[s]), at the time the kernel runs: a stream-ordered copy into the table
+ * recalibrates a camera, and a recorded schedule (rv_sched_*) sees the change
+ * on its next run without being recorded again. */
+typedef struct rv_cam_proj {
+  double H[9];         /* row-major f64 homography (projector.py:69-72) */
+  double max_distance; /* < 0: None */
+  float origin[2];
+  int32_t enabled;     /* 0: this stream's projector is None */
+  int32_t reserved;
+} rv_cam_proj;
+#define RV_CAM_PROJ_BYTES 96 /* sizeof(rv_cam_proj) */
+/* rv_sort_update with stream s projected through cams[s] (device, S entries,
+ * 8-byte aligned; NULL = no stream has a projector).  params6[4] is ignored:
+ * max_distance is the table's.  Everything else as rv_sort_update.
+ * Stream s behaves as SortTracker.update(dets, ts, projector_s) with the
+ * projector the table holds when the call runs.  After a change the speed
+ * history keeps the ground positions it holds, so a speed may span the old
+ * and the new calibration (sort_tracker.py:147-168).  While enabled == 0 a
+ * matched track skips update_metrics and keeps reporting its last
+ * current_distance / current_speed (sort_tracker.py:242-247); a new track
+ * reports None.  rv_sort_update does not do the latter: without a projector
+ * it writes NaN for every detection. */
+int rv_sort_update_cams(void* state_in, void* state_out, int S, int tmax, const float* dets,
+                        const int* dcount, int dmax, const double* ts, const double* params6,
+                        const rv_cam_proj* cams, void* ws, size_t ws_bytes, int* out_id,
+                        double* out_dist, double* out_speed, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Result hand-back (yolo_ultralytics.py:44-52 `.cpu().numpy()` + Detection  */
 /* construction; sort_tracker.py:234-247 fills track_id / distance_m /       */
@@ -557,6 +589,20 @@ int rv_homography_project_f64(const double* H9, const float* boxes, int n,
 int rv_untracked_metrics(const float* dets, const int* det_n, int S, int dmax,
                          const double* H9, const float* origin2, double max_distance,
                          int* out_id, double* out_dist, double* out_speed, void* stream);
+/* The same with stream s projected through cams[s] (device, S entries, as for
+ * rv_sort_update_cams; NULL or enabled == 0: that stream's distances are
+ * NaN). */
+int rv_untracked_metrics_cams(const float* dets, const int* det_n, int S, int dmax,
+                              const rv_cam_proj* cams, int* out_id, double* out_dist,
+                              double* out_speed, void* stream);
+/* rv_homography_project_f64 over a camera table: box i (boxes: n x 4 f32,
+ * device) goes through camera box_cam[i] (device int32, n entries) of cams
+ * (device, S entries).  out_xy (n x 2 f64) and out_dist (nullable, n f64) are
+ * NaN where that camera is disabled or the projection is None; a box_cam
+ * value outside [0, S) gives NaN outputs for that box and reads no entry. */
+int rv_homography_project_cams(const rv_cam_proj* cams, int S, const float* boxes,
+                               const int* box_cam, int n, double* out_xy, double* out_dist,
+                               void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Ingest: NV12 -> BGR (cv2.COLOR_YUV2BGR_NV12, 8U, BT.601 video range,      */
@@ -679,7 +725,9 @@ int rv_capture_close(void* handle);
 #define RV_SCHED_HANDBACK 6               /* rv_results_handback */
 #define RV_SCHED_UNTRACKED 7              /* rv_untracked_metrics */
 #define RV_SCHED_PREPROCESS_CHAIN 8        /* rv_preprocess_chain_u8 */
-#define RV_SCHED_NUM_OPS 9
+#define RV_SCHED_SORT_UPDATE_CAMS 9 /* rv_sort_update_cams */
+#define RV_SCHED_UNTRACKED_CAMS 10 /* rv_untracked_metrics_cams */
+#define RV_SCHED_NUM_OPS 11
 int rv_sched_create(void** handle);
 int rv_sched_destroy(void* handle);
 int rv_sched_add_op(void* handle, int op, const int64_t* iargs, int ni, const double* fargs,

@@ -83,6 +83,8 @@ const OpSpec kSpecs[RV_SCHED_NUM_OPS] = {
     /* RV_SCHED_HANDBACK */ {10, 0},
     /* RV_SCHED_UNTRACKED */ {9, 1},
     /* RV_SCHED_PREPROCESS_CHAIN */ {11, 0},
+    /* RV_SCHED_SORT_UPDATE_CAMS */ {15, 0},
+    /* RV_SCHED_UNTRACKED_CAMS */ {8, 0},
 };
 
 int issue_op(const Node& n) {
@@ -145,6 +147,19 @@ int issue_op(const Node& n) {
                                     (const rv_chain_desc*)host_arg(n, a[6]), P<void>(a[7]),
                                     (size_t)a[8], P<uint8_t>(a[9]),
                                     (const int*)host_arg(n, a[10]), s);
+    case RV_SCHED_SORT_UPDATE_CAMS:
+      // state_in, state_out, S, tmax, dets, dcount, dmax, ts, params6(host), cams (device:
+      // read by every run), ws, ws_bytes, out_id, out_dist, out_speed
+      return rv_sort_update_cams(P<void>(a[0]), P<void>(a[1]), (int)a[2], (int)a[3],
+                                 P<const float>(a[4]), P<const int>(a[5]), (int)a[6],
+                                 P<const double>(a[7]), (const double*)host_arg(n, a[8]),
+                                 P<const rv_cam_proj>(a[9]), P<void>(a[10]), (size_t)a[11],
+                                 P<int>(a[12]), P<double>(a[13]), P<double>(a[14]), s);
+    case RV_SCHED_UNTRACKED_CAMS:
+      // dets, det_n, S, dmax, cams (device), out_id, out_dist, out_speed
+      return rv_untracked_metrics_cams(P<const float>(a[0]), P<const int>(a[1]), (int)a[2],
+                                       (int)a[3], P<const rv_cam_proj>(a[4]), P<int>(a[5]),
+                                       P<double>(a[6]), P<double>(a[7]), s);
   }
   set_error("rv_sched: unknown op %d", n.op);
   return RV_EINVAL;

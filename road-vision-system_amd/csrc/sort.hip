@@ -22,6 +22,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 #include "common.h"
 #include "track_math.h"
@@ -301,6 +302,24 @@ __device__ void kf_update_rows(Track& t, const double z[4], double* sc, int r) {
 #undef KR_A
 }
 
+// rv_sort_update_cams: the launch parameters plus the per-camera table
+// (device, S entries, nullable).  H / origin / max_distance / has_proj of the
+// base are not the launch's: each block fills them from its stream's entry.
+struct SortParamsCams : SortParams {
+  const rv_cam_proj* cams;
+};
+static_assert(sizeof(rv_cam_proj) == RV_CAM_PROJ_BYTES, "rv_cam_proj layout");
+static_assert(sizeof(SortParams) % 8 == 0, "SortParams alignment");
+
+// Word w (32 bits) of a camera entry -> its word in a SortParams (the block's
+// copy of the launch parameters with its stream's projector); -1: not kept.
+__device__ __forceinline__ int cam_word_to_param(int w) {
+  if (w < 18) return (int)offsetof(SortParams, H) / 4 + w;
+  if (w < 20) return (int)offsetof(SortParams, max_distance) / 4 + (w - 18);
+  if (w < 22) return (int)offsetof(SortParams, origin) / 4 + (w - 20);
+  return w == 22 ? (int)offsetof(SortParams, has_proj) / 4 : -1;  // enabled -> has_proj
+}
+
 // HomographyProjector.project_point / GroundProjector.distance (track_math.h)
 __device__ __forceinline__ bool project(const SortParams& p, double x, double y, double& X,
                                         double& Y) {
@@ -390,7 +409,8 @@ __device__ void track_init(Track& t, int id, const float* det, double ts) {
 //   sort_update_kernel     one thread per detection of every stream: KF
 //                          update + metrics of its matched track, or the
 //                          new track's init + metrics; the per-detection
-//                          outputs.
+//                          outputs (sort_update_cams_kernel: the metrics
+//                          through the stream's own camera entry).
 //
 // Tracks live in a fixed per-stream pool of tmax slots; the reference's
 // list order is an index array (order[i] = slot of the i-th track), so a
@@ -475,6 +495,12 @@ __device__ int block_rank(F flag, int n, int* out, int* wtot) {
 }
 
 // The per-detection update of sort_update_kernel for detection row d (job j).
+// p: the launch parameters with the stream's projector (the launch's own, or
+// the block's copy filled from its camera entry).  KEEP (rv_sort_update_cams):
+// a track's stored distance / speed are handed out also while the stream has
+// no projector, as sort_tracker.py:242-247 does when a call's projector is
+// None (a matched track keeps its last values; a new track's are None).
+template <bool KEEP>
 __device__ __forceinline__ void sort_update_row(Track* __restrict__ pool, const float* __restrict__ dets,
                                                 double ts, int s, int d, int2 j, const SortParams& p,
                                                 int* __restrict__ out_id, double* __restrict__ out_dist,
@@ -508,7 +534,7 @@ __device__ __forceinline__ void sort_update_row(Track* __restrict__ pool, const 
   }
   if (p.has_proj) update_metrics(p, tr, de[0], de[1], de[2], de[3], ts);
   out_id[o] = tr.id;
-  if (p.has_proj) {
+  if (KEEP || p.has_proj) {
     if (!isnone(tr.cur_dist)) out_dist[o] = tr.cur_dist;
     if (!isnone(tr.cur_speed)) out_speed[o] = tr.cur_speed * 3.6;
   }
@@ -542,13 +568,23 @@ __device__ unsigned long long g_sort_phase[8];
 // of the predicted boxes and jobs.  A workgroup of NT = 256 threads gives
 // the update's f64 Kalman algebra the whole register file (one wave per
 // SIMD) without spills.
-template <int NT, bool FUSED>
+//
+// PT = SortParamsCams (rv_sort_update_cams, FUSED only: the three-launch
+// form projects in sort_update_cams_kernel): on entry the block builds, in
+// LDS behind the jobs, a copy of the launch parameters with its stream's
+// camera entry as the projector (one coalesced 96-byte read) and the update
+// phase takes its parameters from there, so the serial f64 chain of the
+// update never waits on HBM for the table and nothing is held in registers
+// across the association.
+template <int NT, bool FUSED, class PT = SortParams>
 __global__ __launch_bounds__(NT) void sort_associate_kernel(
     StreamHdr* __restrict__ hdr, int* __restrict__ order, Track* __restrict__ pool,
     const float* __restrict__ dets, const int* __restrict__ dcount,
-    const double* __restrict__ ts_arr, SortParams p, SortWs ws, int* __restrict__ out_id,
+    const double* __restrict__ ts_arr, PT p, SortWs ws, int* __restrict__ out_id,
     double* __restrict__ out_dist, double* __restrict__ out_speed) {
   constexpr int kAssocThreads = NT;
+  constexpr bool CAMS = !std::is_same<PT, SortParams>::value;
+  static_assert(!CAMS || FUSED, "the camera table is read by the kernel that runs the metrics");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int kUpd = NT < kUpdLanes ? NT : kUpdLanes;  // FUSED: threads running the KF updates
   float4* tbox = (float4*)smem;                     // tmax
@@ -567,10 +603,28 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
   // scratch (kUpd x 126 doubles, which reuses the dead association arrays
   // from offset 0 once the bookkeeping is done)
   int2* ljob = (int2*)(smem + sort_ljob_off(p.tmax, p.dmax, kUpd));
+  // CAMS: the parameters with the stream's projector, behind the jobs (8-byte aligned)
+  SortParams* lpar = (SortParams*)(ljob + p.dmax);
   __shared__ int s_cnt, s_red_v[16], s_red_i[16], wtot[16];
 
   const int s = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
+  if constexpr (CAMS) {
+    // a NULL table is a table of disabled entries; visible to the update
+    // phase through the barriers in between
+    if (tid < RV_CAM_PROJ_BYTES / 4) {
+      const int w = cam_word_to_param(tid);
+      const uint32_t v = p.cams ? ((const uint32_t*)(p.cams + s))[tid] : 0u;
+      if (w >= 0) ((uint32_t*)lpar)[w] = v;
+    } else if (tid == 64) {  // another wave: the launch's own fields
+      lpar->max_staleness = p.max_staleness;
+      lpar->iou_thr = p.iou_thr;
+      lpar->speed_window = p.speed_window;
+      lpar->min_hits = p.min_hits;
+      lpar->tmax = p.tmax;
+      lpar->dmax = p.dmax;
+    }
+  }
 #ifdef RV_SORT_PHASE
   unsigned long long ph_t = wall_clock64();
   if (threadIdx.x == 0) atomicAdd(&g_sort_phase[7], 1ull);  // blocks timed
@@ -829,6 +883,9 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
     // states are this block's own global writes, visible after the barrier
     __syncthreads();
     RV_PH(4);  // bookkeeping
+    // the rows' parameters: the launch's (a kernel argument) or the block's
+    // copy with its stream's projector
+    const SortParams& q = *(CAMS ? (const SortParams*)lpar : (const SortParams*)&p);
     if (D <= NT / 8 && D <= kUpd) {
       // one 8-lane group per detection: the matched tracks' KF updates row
       // by row (kf_update_rows), then lane 0 of the group does the rest of
@@ -844,15 +901,17 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
         kf_update_rows(pl[j.x], z, (double*)smem + (size_t)d * kKfRows, r);
       }
       if (r == 0 && d < D)
-        sort_update_row(pool, dets, ts, s, d, j, p, out_id, out_dist, out_speed, nullptr, 0,
-                        matched);
+        sort_update_row<CAMS>(pool, dets, ts, s, d, j, q, out_id, out_dist, out_speed, nullptr, 0,
+                              matched);
       for (int e = D + tid; e < p.dmax; e += NT)
-        sort_update_row(pool, dets, ts, s, e, ljob[e], p, out_id, out_dist, out_speed, nullptr, 0);
+        sort_update_row<CAMS>(pool, dets, ts, s, e, ljob[e], q, out_id, out_dist, out_speed,
+                              nullptr, 0);
     } else {
       double* ap = (double*)smem + tid;
       if (tid < kUpd)
         for (int d = tid; d < p.dmax; d += kUpd)
-          sort_update_row(pool, dets, ts, s, d, ljob[d], p, out_id, out_dist, out_speed, ap, kUpd);
+          sort_update_row<CAMS>(pool, dets, ts, s, d, ljob[d], q, out_id, out_dist, out_speed, ap,
+                                kUpd);
     }
     RV_PH(5);  // KF updates + metrics
   }
@@ -879,8 +938,31 @@ __global__ __launch_bounds__(kUpdLanes) void sort_update_kernel(
   const int s = blockIdx.y;
   const int d = blockIdx.x * kUpdLanes + threadIdx.x;
   if (d >= p.dmax) return;
-  sort_update_row(pool, dets, ts_arr[s], s, d, ws.det_job[(size_t)s * p.dmax + d], p, out_id,
-                  out_dist, out_speed, ap + threadIdx.x, kUpdLanes);
+  sort_update_row<false>(pool, dets, ts_arr[s], s, d, ws.det_job[(size_t)s * p.dmax + d], p,
+                         out_id, out_dist, out_speed, ap + threadIdx.x, kUpdLanes);
+}
+
+// The same for rv_sort_update_cams: the block's stream is blockIdx.y, so its
+// camera entry is read once, on entry, from a block-uniform address.
+__global__ __launch_bounds__(kUpdLanes) void sort_update_cams_kernel(
+    Track* __restrict__ pool, const float* __restrict__ dets, const double* __restrict__ ts_arr,
+    SortParams p, const rv_cam_proj* __restrict__ cams, SortWs ws, int* __restrict__ out_id,
+    double* __restrict__ out_dist, double* __restrict__ out_speed) {
+  __shared__ double ap[126 * kUpdLanes];  // KF update scratch (kKfScratch), element-major
+  const int s = blockIdx.y;
+  const int d = blockIdx.x * kUpdLanes + threadIdx.x;
+  p.has_proj = 0;
+  if (cams) {
+    const rv_cam_proj cam = cams[s];
+    for (int i = 0; i < 9; ++i) p.H[i] = cam.H[i];
+    p.origin[0] = cam.origin[0];
+    p.origin[1] = cam.origin[1];
+    p.max_distance = cam.max_distance;
+    p.has_proj = cam.enabled;
+  }
+  if (d >= p.dmax) return;
+  sort_update_row<true>(pool, dets, ts_arr[s], s, d, ws.det_job[(size_t)s * p.dmax + d], p,
+                        out_id, out_dist, out_speed, ap + threadIdx.x, kUpdLanes);
 }
 
 // Per-stream state layout: headers (S x 16 B, padded to 256 B), the list
@@ -994,24 +1076,28 @@ extern "C" int rv_sort_init(void* state, int S, int tmax, void* stream) {
   return hipStreamSynchronize(as_stream(stream)) == hipSuccess ? RV_OK : RV_EINVAL;
 }
 
-extern "C" int rv_sort_update(void* state_in, void* state_out, int S, int tmax,
-                              const float* dets, const int* dcount, int dmax, const double* ts,
-                              const double* params6, const double* H9, const float* origin2,
-                              void* ws, size_t ws_bytes, int* out_id, double* out_dist,
-                              double* out_speed, void* stream) {
+// rv_sort_update (use_cams false: H9 / origin2 / params6[4], cams unused) and
+// rv_sort_update_cams (use_cams true: the device table, nullable).
+static int sort_update_any(void* state_in, void* state_out, int S, int tmax, const float* dets,
+                           const int* dcount, int dmax, const double* ts, const double* params6,
+                           const double* H9, const float* origin2, bool use_cams,
+                           const rv_cam_proj* cams, void* ws, size_t ws_bytes, int* out_id,
+                           double* out_dist, double* out_speed, void* stream) {
   RV_CHECK_ARG(state_in && state_out, "null state");
   RV_CHECK_ARG(dets && dcount && ts && params6 && out_id && out_dist && out_speed && ws,
                "null pointer");
   RV_CHECK_ARG(S > 0 && tmax > 0 && tmax <= 8192 && dmax > 0 && dmax <= 4096, "bad sizes");
   RV_CHECK_ARG(ws_bytes >= rv_sort_ws_bytes(S, tmax, dmax), "workspace too small");
   RV_CHECK_ARG((size_t)tmax * dmax < 0xFFFFFFFFull, "tmax*dmax too large");
-  SortParams p;
+  RV_CHECK_ARG(((uintptr_t)cams & 7) == 0, "cams is not 8-byte aligned");
+  SortParamsCams p;
   memset(&p, 0, sizeof(p));
   p.max_staleness = params6[0];
   p.min_hits = (int)params6[1];
   p.iou_thr = params6[2];
   p.speed_window = params6[3];
-  p.max_distance = params6[4];
+  p.max_distance = use_cams ? -1.0 : params6[4];
+  p.cams = cams;
   p.tmax = tmax;
   p.dmax = dmax;
   p.has_proj = H9 != nullptr;
@@ -1022,7 +1108,8 @@ extern "C" int rv_sort_update(void* state_in, void* state_out, int S, int tmax,
     p.origin[1] = origin2[1];
   }
   const bool fused = sort_fused();
-  const size_t smem = sort_smem(tmax, dmax, fused);
+  // the fused cams kernel keeps its stream's parameters behind the jobs
+  const size_t smem = sort_smem(tmax, dmax, fused) + (use_cams && fused ? sizeof(SortParams) : 0);
   RV_CHECK_ARG(smem <= 160 * 1024, "tmax/dmax need %zu B of LDS", smem);
   hipStream_t st = as_stream(stream);
   int r = RV_OK;
@@ -1031,17 +1118,23 @@ extern "C" int rv_sort_update(void* state_in, void* state_out, int S, int tmax,
                                  hipMemcpyDeviceToDevice, st),
                   "rv_sort_update state copy");
   if (r) return r;
-  static int attr_set[2] = {0, 0};
-  const void* assoc_fn = fused ? (const void*)sort_associate_kernel<kFusedThreads, true>
-                               : (const void*)sort_associate_kernel<kAssocThreads, false>;
-  if ((int)smem > attr_set[fused]) {  // once per growth, outside steady-state launches
+  // the association kernel that runs: [0] three-launch, [1] fused, [2] fused
+  // with the camera table (the three-launch form reads the table in its
+  // update kernel, so its association kernel is [0] either way)
+  static int attr_set[3] = {0, 0, 0};
+  const int form = fused ? (use_cams ? 2 : 1) : 0;
+  const void* assoc_fn =
+      form == 2   ? (const void*)sort_associate_kernel<kFusedThreads, true, SortParamsCams>
+      : form == 1 ? (const void*)sort_associate_kernel<kFusedThreads, true>
+                  : (const void*)sort_associate_kernel<kAssocThreads, false>;
+  if ((int)smem > attr_set[form]) {  // once per growth, outside steady-state launches
     hipError_t e = hipFuncSetAttribute(assoc_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) {
       set_error("hipFuncSetAttribute(%zu B LDS): %s", smem, hipGetErrorString(e));
       (void)hipGetLastError();
       return -(int)e;
     }
-    attr_set[fused] = (int)smem;
+    attr_set[form] = (int)smem;
   }
   const StateView v = state_view(state_out, S, tmax);
   size_t off[4];
@@ -1051,9 +1144,15 @@ extern "C" int rv_sort_update(void* state_in, void* state_out, int S, int tmax,
   w.tbox = (float4*)((uint8_t*)ws + off[1]);
   w.tupd = (double*)((uint8_t*)ws + off[2]);
   w.det_job = (int2*)((uint8_t*)ws + off[3]);
+  const SortParams& pb = p;  // the launch parameters without the table
+  if (form == 2) {
+    sort_associate_kernel<kFusedThreads, true, SortParamsCams><<<S, kFusedThreads, smem, st>>>(
+        v.hdr, v.order, v.pool, dets, dcount, ts, p, w, out_id, out_dist, out_speed);
+    return launch_status("rv_sort_update_cams (fused)");
+  }
   if (fused) {
     sort_associate_kernel<kFusedThreads, true><<<S, kFusedThreads, smem, st>>>(
-        v.hdr, v.order, v.pool, dets, dcount, ts, p, w, out_id, out_dist, out_speed);
+        v.hdr, v.order, v.pool, dets, dcount, ts, pb, w, out_id, out_dist, out_speed);
     return launch_status("rv_sort_update (fused)");
   }
   sort_predict_kernel<<<dim3(ceil_div(tmax, 256), S), 256, 0, st>>>(v.hdr, v.order, v.pool, ts,
@@ -1061,12 +1160,37 @@ extern "C" int rv_sort_update(void* state_in, void* state_out, int S, int tmax,
   r = launch_status("rv_sort_update (predict)");
   if (r) return r;
   sort_associate_kernel<kAssocThreads, false><<<S, kAssocThreads, smem, st>>>(
-      v.hdr, v.order, v.pool, dets, dcount, ts, p, w, out_id, out_dist, out_speed);
+      v.hdr, v.order, v.pool, dets, dcount, ts, pb, w, out_id, out_dist, out_speed);
   r = launch_status("rv_sort_update (associate)");
   if (r) return r;
+  if (use_cams) {
+    sort_update_cams_kernel<<<dim3(ceil_div(dmax, kUpdLanes), S), kUpdLanes, 0, st>>>(
+        v.pool, dets, ts, pb, cams, w, out_id, out_dist, out_speed);
+    return launch_status("rv_sort_update_cams (update)");
+  }
   sort_update_kernel<<<dim3(ceil_div(dmax, kUpdLanes), S), kUpdLanes, 0, st>>>(
-      v.pool, dets, ts, p, w, out_id, out_dist, out_speed);
+      v.pool, dets, ts, pb, w, out_id, out_dist, out_speed);
   return launch_status("rv_sort_update (update)");
+}
+
+extern "C" int rv_sort_update(void* state_in, void* state_out, int S, int tmax,
+                              const float* dets, const int* dcount, int dmax, const double* ts,
+                              const double* params6, const double* H9, const float* origin2,
+                              void* ws, size_t ws_bytes, int* out_id, double* out_dist,
+                              double* out_speed, void* stream) {
+  return sort_update_any(state_in, state_out, S, tmax, dets, dcount, dmax, ts, params6, H9,
+                         origin2, false, nullptr, ws, ws_bytes, out_id, out_dist, out_speed,
+                         stream);
+}
+
+extern "C" int rv_sort_update_cams(void* state_in, void* state_out, int S, int tmax,
+                                   const float* dets, const int* dcount, int dmax,
+                                   const double* ts, const double* params6,
+                                   const rv_cam_proj* cams, void* ws, size_t ws_bytes,
+                                   int* out_id, double* out_dist, double* out_speed,
+                                   void* stream) {
+  return sort_update_any(state_in, state_out, S, tmax, dets, dcount, dmax, ts, params6, nullptr,
+                         nullptr, true, cams, ws, ws_bytes, out_id, out_dist, out_speed, stream);
 }
 
 extern "C" int rv_sort_export(const void* state, int S, int tmax, double* x_out, int* meta,

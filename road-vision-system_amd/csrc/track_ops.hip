@@ -8,6 +8,9 @@
 //   rv_homography_project_f64 project_bbox + distance, projector.py:30-47,74-84
 //   rv_untracked_metrics      the tracker-off branch of main_preview.py:101-109:
 //                             no track ids or speeds, distance_for_bbox per det
+//   rv_homography_project_cams / rv_untracked_metrics_cams
+//                             the two above with one projector per camera
+//                             stream, from a table in device memory
 //
 // All latency-bound small work: one workgroup per stream for the IoU and
 // the assignment, one thread per box for the projection.
@@ -169,6 +172,62 @@ __global__ void untracked_metrics_kernel(const float* __restrict__ dets,
   out_speed[i] = NAN;
 }
 
+// The two entries above over a per-camera table (device, one entry per
+// stream, read when the kernel runs).
+static_assert(sizeof(rv_cam_proj) == RV_CAM_PROJ_BYTES, "rv_cam_proj layout");
+
+// Box i through camera box_cam[i]; an index outside [0, S), a disabled
+// camera and a None projection all give NaN (no entry is read for the first).
+__global__ void project_cams_kernel(const rv_cam_proj* __restrict__ cams, int S,
+                                    const float* __restrict__ boxes,
+                                    const int* __restrict__ box_cam, int n,
+                                    double* __restrict__ out_xy, double* __restrict__ out_dist) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double X = NAN, Y = NAN, dist = NAN;
+  const int c = box_cam[i];
+  if (c >= 0 && c < S && cams[c].enabled) {
+    const rv_cam_proj cam = cams[c];
+    const float* b = boxes + 4 * (size_t)i;
+    const double cx = 0.5 * ((double)b[0] + (double)b[2]);
+    const double cy = (double)b[3];
+    double px, py;
+    if (project_h(cam.H, cx, cy, px, py)) {
+      X = px;
+      Y = py;
+      dist = distance_o(cam.origin, cam.max_distance, px, py);
+    }
+  }
+  out_xy[2 * (size_t)i] = X;
+  out_xy[2 * (size_t)i + 1] = Y;
+  if (out_dist) out_dist[i] = dist;
+}
+
+// untracked_metrics_kernel with stream s's projector taken from cams[s]
+// (cams nullable: no stream has one).
+__global__ void untracked_metrics_cams_kernel(const float* __restrict__ dets,
+                                              const int* __restrict__ det_n, int S, int dmax,
+                                              const rv_cam_proj* __restrict__ cams,
+                                              int* __restrict__ out_id,
+                                              double* __restrict__ out_dist,
+                                              double* __restrict__ out_speed) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S * dmax) return;
+  const int s = i / dmax, d = i - s * dmax;
+  double dist = NAN;
+  if (cams && d < min(max(det_n[s], 0), dmax) && cams[s].enabled) {
+    const rv_cam_proj cam = cams[s];
+    const float* b = dets + 6 * (size_t)i;
+    const double cx = 0.5 * ((double)b[0] + (double)b[2]);
+    const double cy = (double)b[3];
+    double X, Y;
+    if (project_h(cam.H, cx, cy, X, Y)) dist = distance_o(cam.origin, cam.max_distance, X, Y);
+  }
+  out_id[i] = -1;
+  out_dist[i] = dist;
+  out_speed[i] = NAN;
+}
+
 }  // namespace
 
 extern "C" int rv_iou_matrix_batched(const float* trk, const int* T, const float* det,
@@ -239,6 +298,35 @@ extern "C" int rv_untracked_metrics(const float* dets, const int* det_n, int S, 
   untracked_metrics_kernel<<<ceil_div(n, 256), 256, 0, as_stream(stream)>>>(
       dets, det_n, S, dmax, p, out_id, out_dist, out_speed);
   return launch_status("rv_untracked_metrics");
+}
+
+extern "C" int rv_untracked_metrics_cams(const float* dets, const int* det_n, int S, int dmax,
+                                         const rv_cam_proj* cams, int* out_id, double* out_dist,
+                                         double* out_speed, void* stream) {
+  RV_CHECK_ARG(dets != nullptr && det_n != nullptr && out_id != nullptr && out_dist != nullptr &&
+                   out_speed != nullptr,
+               "null pointer");
+  RV_CHECK_ARG(S >= 0 && dmax >= 1, "bad shape S=%d dmax=%d", S, dmax);
+  RV_CHECK_ARG((size_t)S * dmax < (1u << 30), "S*dmax too large");
+  RV_CHECK_ARG(((uintptr_t)cams & 7) == 0, "cams is not 8-byte aligned");
+  if (S == 0) return RV_OK;
+  const int n = S * dmax;
+  untracked_metrics_cams_kernel<<<ceil_div(n, 256), 256, 0, as_stream(stream)>>>(
+      dets, det_n, S, dmax, cams, out_id, out_dist, out_speed);
+  return launch_status("rv_untracked_metrics_cams");
+}
+
+extern "C" int rv_homography_project_cams(const rv_cam_proj* cams, int S, const float* boxes,
+                                          const int* box_cam, int n, double* out_xy,
+                                          double* out_dist, void* stream) {
+  RV_CHECK_ARG(cams != nullptr && out_xy != nullptr && (n == 0 || (boxes != nullptr && box_cam != nullptr)),
+               "null pointer");
+  RV_CHECK_ARG(S >= 1 && n >= 0, "bad shape S=%d n=%d", S, n);
+  RV_CHECK_ARG(((uintptr_t)cams & 7) == 0, "cams is not 8-byte aligned");
+  if (n == 0) return RV_OK;
+  project_cams_kernel<<<ceil_div(n, 256), 256, 0, as_stream(stream)>>>(cams, S, boxes, box_cam, n,
+                                                                       out_xy, out_dist);
+  return launch_status("rv_homography_project_cams");
 }
 
 }  // namespace rv

@@ -168,6 +168,14 @@ _SIGS = {
     "rv_sort_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    # per-camera projector table (device, rv_cam_proj x S)
+    "rv_sort_update_cams": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+    "rv_untracked_metrics_cams": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    "rv_homography_project_cams": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                           c_void_p, c_void_p]),
     "rv_sort_stats": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rv_sort_export": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
@@ -213,7 +221,8 @@ def check(status: int, what: str = "") -> None:
 # stream-ordered calls a launch schedule can record (rvs_amd.schedule._OPS)
 _RECORDABLE = {"rv_clahe_median_letterbox_u8", "rv_clahe_median_u8", "rv_letterbox_u8",
                "rv_yolo_forward_part", "rv_nms_postprocess", "rv_sort_update",
-               "rv_results_handback", "rv_untracked_metrics", "rv_preprocess_chain_u8"}
+               "rv_results_handback", "rv_untracked_metrics", "rv_preprocess_chain_u8",
+               "rv_sort_update_cams", "rv_untracked_metrics_cams"}
 
 _NOCHECK = {"rv_preprocess_chain_route", "rv_sched_num_nodes", "rv_sched_event_query", "rv_abi_version", "rv_cand_segments", "rv_yolo_cand_segments", "rv_clahe_median_fits", "rv_clahe_median_letterbox_fits", "rv_yolo_num_convs", "rv_yolo_num_anchors",
             "rv_yolo_num_buffers", "rv_yolo_trace", "rv_yolo_profile_read", "rv_yolo_tuned_config",

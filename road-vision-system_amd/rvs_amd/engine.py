@@ -12,7 +12,7 @@ step.  ``results()`` converts one step's device outputs into the reference's
 from __future__ import annotations
 
 import warnings
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -22,17 +22,24 @@ from .config import load_config
 from .detect.types import Detection
 from .detect.weights import detector_weights, names_from_config, variant_of
 from .detect.yolo_hip import YoloEngine
-from .geometry import GroundProjector, build_projector
+from .geometry import GroundProjector, build_camera_projectors, build_projector
 from .handback import Record, handback
 from .preprocess import PreprocessPipeline
-from .track.sort_hip import MultiStreamSort
+from .track.sort_hip import CameraTable, MultiStreamSort
 
 
 class RoadVisionEngine:
     def __init__(self, cfg: Optional[dict], n_streams: int, frame_hw, device="cuda",
                  tmax: int = 1024, projector: Optional[GroundProjector] = None,
-                 weights: Optional[np.ndarray] = None, lanes: int = 1, pair: int = 1):
-        """pair = P >= 2: the pipelined schedule (schedule.PipelinedRun)
+                 weights: Optional[np.ndarray] = None, lanes: int = 1, pair: int = 1,
+                 projectors: Optional[Sequence[Optional[GroundProjector]]] = None):
+        """projectors: one ground projector (or None) per camera stream, as
+        the reference runs one process -- one geometry.projector -- per
+        camera; default: the config's geometry.cameras, when present.  It
+        wins over `projector` / geometry.projector (one calibration for every
+        stream).  set_camera_projector recalibrates one camera later.
+
+        pair = P >= 2: the pipelined schedule (schedule.PipelinedRun)
         runs the forwards of P consecutive steps as one batch of P*S frames
         (the small P4 / P5 layers amortise their per-launch floor; measured
         B = 64: 20.5 us per frame against 25.0 at B = 32,
@@ -78,8 +85,17 @@ class RoadVisionEngine:
             int(det_cfg.get("max_det", 100))
         # main_preview.py:64-78: a tracker or projector that fails to build
         # is reported and left off (the run goes on without that feature)
-        if projector is None:
-            geom = cfg.get("geometry", {}) or {}
+        geom = cfg.get("geometry", {}) or {}
+        if projectors is None and projector is None and geom.get("enabled", False):
+            # geometry.cameras: one projector mapping (or null) per stream
+            projectors = build_camera_projectors(geom, self.S)
+        if projectors is not None:
+            projectors = list(projectors)
+            if len(projectors) != self.S:
+                raise ValueError(f"{len(projectors)} projectors for {self.S} camera streams")
+            projector = None
+        self.projectors = projectors
+        if projector is None and projectors is None:
             if geom.get("enabled", False):
                 try:
                     projector = build_projector(geom)
@@ -92,7 +108,10 @@ class RoadVisionEngine:
             try:
                 tracker = MultiStreamSort(trk_cfg, self.S, tmax=tmax, dmax=self.max_det,
                                           device=self.device)
-                tracker.set_projector(projector)
+                if projectors is not None:
+                    tracker.set_projectors(projectors)
+                else:
+                    tracker.set_projector(projector)
                 self.tracker = tracker
             except Exception as exc:
                 warnings.warn(f"tracker init failed, running without it: {exc}")
@@ -100,7 +119,8 @@ class RoadVisionEngine:
         if self.tracker is None and self.detector is not None:
             # tracker off (main_preview.py:104-109): ids and speeds stay None,
             # each detection gets projector.distance_for_bbox when a projector exists
-            self._untracked = _UntrackedMetrics(self.S, self.max_det, projector, self.device)
+            self._untracked = _UntrackedMetrics(self.S, self.max_det, projector, self.device,
+                                                projectors=projectors)
         self.proc = torch.empty((self.S, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
         self.names = names_from_config(det_cfg, self.nc)
         # result hand-back: device staging buffer + the pinned host record of step()
@@ -294,6 +314,29 @@ class RoadVisionEngine:
             res.append(lst)
         return res
 
+    def set_camera_projector(self, s: int, projector: Optional[GroundProjector]) -> None:
+        """Recalibrate camera stream s (None: remove its projector) for every
+        later step: one stream-ordered copy into the device table on the
+        current stream (MultiStreamSort.set_camera_projector, or the
+        tracker-off metrics' table).  A recorded PipelinedRun reads the same
+        table, so it follows the change without being recorded again -- but
+        call this between its runs (after the previous run has been waited
+        for), not while one is in flight: the run's SORT launches are on
+        other streams and would see the copy at an undefined step.  An engine
+        built with a single projector switches to a table in which every
+        other camera keeps that projector; a PipelinedRun recorded before
+        that switch still holds the single-projector calls."""
+        if not 0 <= int(s) < self.S:
+            raise IndexError(f"camera {s} outside [0, {self.S})")
+        if self.tracker is not None:
+            self.tracker.set_camera_projector(s, projector)
+        elif self.detector is not None:
+            self._untracked.set_camera_projector(s, projector)
+        if self.projectors is None:
+            self.projectors = [self.projector] * self.S
+            self.projector = None
+        self.projectors[int(s)] = projector
+
     def track_stats(self) -> Dict[str, np.ndarray]:
         """Per-stream SORT capacity report (MultiStreamSort.stats); empty
         arrays when tracking is off."""
@@ -314,8 +357,19 @@ class _UntrackedMetrics:
     else None -- on the device (rv_untracked_metrics), so the step's
     hand-back record is built exactly as with the tracker."""
 
-    def __init__(self, S: int, dmax: int, projector: Optional[GroundProjector], device):
+    def __init__(self, S: int, dmax: int, projector: Optional[GroundProjector], device,
+                 projectors: Optional[Sequence[Optional[GroundProjector]]] = None):
+        """projectors (length S, entries may be None): one projector per
+        camera stream from a table in device memory
+        (rv_untracked_metrics_cams); it wins over `projector`."""
         self.S, self.dmax = int(S), int(dmax)
+        self.cams = None
+        if projectors is not None:
+            if len(projectors) != self.S:
+                raise ValueError(f"{len(projectors)} projectors for {self.S} camera streams")
+            self.cams = CameraTable(projectors, device)
+            projector = None
+        self._single = projector
         self.out_id = torch.empty((self.S, self.dmax), dtype=torch.int32, device=device)
         self.out_dist = torch.empty((self.S, self.dmax), dtype=torch.float64, device=device)
         self.out_speed = torch.empty((self.S, self.dmax), dtype=torch.float64, device=device)
@@ -327,10 +381,24 @@ class _UntrackedMetrics:
             self._origin = np.ascontiguousarray(origin, np.float32)
             self._md = float(md)
 
+    def set_camera_projector(self, s: int, projector: Optional[GroundProjector]) -> None:
+        """Recalibrate camera s (stream-ordered copy on the current stream);
+        without a table yet the other cameras start from the single projector."""
+        if not 0 <= int(s) < self.S:
+            raise IndexError(f"camera {s} outside [0, {self.S})")
+        if self.cams is None:
+            self.cams = CameraTable([self._single] * self.S, self.out_id.device)
+        self.cams.set(s, projector)
+
     def __call__(self, dets: torch.Tensor, det_n: torch.Tensor):
         S = dets.shape[0]
         if S != self.S or dets.shape[1] != self.dmax:
             raise ValueError(f"dets must be ({self.S}, {self.dmax}, 6)")
+        if self.cams is not None:
+            _lib.call("rv_untracked_metrics_cams", _lib.ptr(dets), _lib.ptr(det_n), S, self.dmax,
+                      _lib.ptr(self.cams.dev), _lib.ptr(self.out_id), _lib.ptr(self.out_dist),
+                      _lib.ptr(self.out_speed), _lib.stream_ptr())
+            return self.out_id, self.out_dist, self.out_speed
         _lib.call("rv_untracked_metrics", _lib.ptr(dets), _lib.ptr(det_n), S, self.dmax,
                   self._H.ctypes.data if self._H is not None else None,
                   self._origin.ctypes.data if self._origin is not None else None, self._md,

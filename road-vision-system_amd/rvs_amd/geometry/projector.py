@@ -15,6 +15,7 @@ projection given H is pinned against the reference (tests/golden).
 """
 from __future__ import annotations
 
+import warnings
 from abc import ABC, abstractmethod
 from typing import Optional, Sequence, Tuple
 
@@ -143,6 +144,62 @@ class HomographyProjector(GroundProjector):
     def device_params(self):
         md = -1.0 if self.max_distance is None else float(self.max_distance)
         return self._H.ravel().astype(np.float64), self.origin.astype(np.float32), md
+
+
+# One entry of the per-camera projector table the *_cams entries read from
+# device memory (rv_cam_proj, include/rvhip.h): 96 bytes per camera stream.
+RV_CAM_PROJ_BYTES = 96
+CAM_PROJ_DTYPE = np.dtype({
+    "names": ["H", "max_distance", "origin", "enabled", "reserved"],
+    "formats": [("<f8", (9,)), "<f8", ("<f4", (2,)), "<i4", "<i4"],
+    "offsets": [0, 72, 80, 88, 92],
+    "itemsize": RV_CAM_PROJ_BYTES,
+})
+
+
+def pack_cam_table(projectors: Sequence[Optional[GroundProjector]]) -> np.ndarray:
+    """The table of S cameras as a (S,) CAM_PROJ_DTYPE array (S x 96 bytes,
+    ready to copy to the device): entry s holds projectors[s].device_params();
+    None gives a disabled entry (enabled = 0, max_distance = -1)."""
+    tab = np.zeros(len(projectors), CAM_PROJ_DTYPE)
+    tab["max_distance"] = -1.0
+    for s, p in enumerate(projectors):
+        if p is None:
+            continue
+        H, origin, md = p.device_params()
+        tab["H"][s] = np.asarray(H, np.float64).reshape(9)
+        tab["origin"][s] = np.asarray(origin, np.float32).reshape(2)
+        tab["max_distance"][s] = float(md)
+        tab["enabled"][s] = 1
+    return tab
+
+
+def build_camera_projectors(geom: dict, n_streams: int) -> Optional[list]:
+    """geometry.cameras -> one projector (or None) per camera stream, or None
+    when the key is absent.  Each entry is a projector mapping (type,
+    image_points, world_points, origin, max_distance) or null; an entry that
+    fails to build warns and leaves that camera without a projector (as
+    main_preview.py:74-78 does for the single one).  A list whose length is
+    not n_streams is a ValueError."""
+    cams = geom.get("cameras") if isinstance(geom, dict) else None
+    if cams is None:
+        return None
+    if not isinstance(cams, (list, tuple)) or len(cams) != int(n_streams):
+        n = len(cams) if isinstance(cams, (list, tuple)) else type(cams).__name__
+        raise ValueError(f"geometry.cameras must list one projector (or null) per camera "
+                         f"stream: got {n}, expected {int(n_streams)}")
+    out = []
+    for s, c in enumerate(cams):
+        if c is None:
+            out.append(None)
+            continue
+        try:
+            out.append(build_projector(c))
+        except Exception as exc:
+            warnings.warn(f"geometry projector of camera {s} failed to build, "
+                          f"running that camera without it: {exc}")
+            out.append(None)
+    return out
 
 
 def build_projector(cfg: dict) -> GroundProjector:

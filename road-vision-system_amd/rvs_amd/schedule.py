@@ -55,6 +55,9 @@ _OPS = {
     "rv_results_handback": (6, 10, {}),
     "rv_untracked_metrics": (7, 10, {4: 72, 5: 8}),
     "rv_preprocess_chain_u8": (8, 11, {6: 120, 10: 24}),
+    # cams is a device pointer (an integer argument): every run reads the table
+    "rv_sort_update_cams": (9, 15, {8: 48}),
+    "rv_untracked_metrics_cams": (10, 8, {}),
 }
 _FLOAT = (ctypes.c_float, ctypes.c_double)
 

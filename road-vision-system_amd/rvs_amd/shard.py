@@ -30,6 +30,19 @@ def partition(total_streams: int, world: int) -> List[range]:
     return [rank_streams(total_streams // world, r) for r in range(world)]
 
 
+def rank_cameras(cameras, streams_per_rank: int, rank: int) -> list:
+    """The slice of a global per-camera list (geometry.cameras entries or
+    projectors, one per global stream id) that rank_streams assigns to
+    `rank`: what that rank's engine takes as its `projectors` /
+    geometry.cameras.  The list must cover the rank's block."""
+    ids = rank_streams(streams_per_rank, rank)
+    cameras = list(cameras)
+    if len(cameras) < ids.stop:
+        raise ValueError(f"{len(cameras)} cameras do not cover rank {rank}'s streams "
+                         f"[{ids.start}, {ids.stop})")
+    return cameras[ids.start:ids.stop]
+
+
 def max_over_ranks(value: float, device=None) -> float:
     """Max of a per-rank scalar (the timed region) over the process group;
     the identity without one."""

@@ -6,14 +6,17 @@ advances all of them by one frame per call, in place (rv_sort_update: KF
 predict over every track, one workgroup per stream for the association and
 bookkeeping, KF update / new tracks over every detection; f64 KF, f32 IoU,
 greedy association identical to the reference's argmax loop, ground
-metrics).  ``SortTracker``
+metrics).  The ground projector is one for all streams (``set_projector``) or
+one per camera stream, held in a ``CameraTable`` in device memory
+(``set_projectors`` / ``set_camera_projector``, rv_sort_update_cams).
+``SortTracker``
 is the reference's single-stream ``Tracker.update(detections, timestamp,
 projector)`` on top of it, mutating and returning the same Detection objects
 (sort_tracker.py:212-278).
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Optional
+from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -21,8 +24,41 @@ import torch
 from .. import _lib
 from .._lib import call, ptr, stream_ptr
 from ..detect.types import Detection
-from ..geometry import GroundProjector
+from ..geometry import RV_CAM_PROJ_BYTES, GroundProjector, pack_cam_table
 from .base import Tracker
+
+
+class CameraTable:
+    """The per-camera projector table of the ``*_cams`` entries (rv_cam_proj,
+    include/rvhip.h) in device memory: entry s is camera stream s's
+    projector, None = that camera has none.  The kernels read it when they
+    run, so ``set`` / ``set_all`` (stream-ordered copies on the current
+    stream into the same buffer) recalibrate cameras for every later launch,
+    those of an already recorded schedule included."""
+
+    def __init__(self, projectors: Sequence[Optional[GroundProjector]], device):
+        self.projectors = list(projectors)
+        self.S = len(self.projectors)
+        self.dev = torch.empty((self.S, RV_CAM_PROJ_BYTES), dtype=torch.uint8, device=device)
+        self.set_all(self.projectors)
+
+    @staticmethod
+    def _rows(projectors) -> torch.Tensor:
+        tab = pack_cam_table(projectors)
+        return torch.from_numpy(tab.view(np.uint8).reshape(len(tab), RV_CAM_PROJ_BYTES))
+
+    def set_all(self, projectors: Sequence[Optional[GroundProjector]]) -> None:
+        projectors = list(projectors)
+        if len(projectors) != self.S:
+            raise ValueError(f"{len(projectors)} projectors for {self.S} camera streams")
+        self.dev.copy_(self._rows(projectors))
+        self.projectors = projectors
+
+    def set(self, s: int, projector: Optional[GroundProjector]) -> None:
+        if not 0 <= int(s) < self.S:
+            raise IndexError(f"camera {s} outside [0, {self.S})")
+        self.dev[int(s)].copy_(self._rows([projector])[0])
+        self.projectors[int(s)] = projector
 
 
 class MultiStreamSort:
@@ -46,12 +82,46 @@ class MultiStreamSort:
         self.params = np.zeros(6, np.float64)
         self._H = None
         self._origin = None
+        self._single = None  # set_projector's projector
+        self.cams: Optional[CameraTable] = None  # set_projectors: one projector per stream
         self.reset()
 
     def reset(self):
         call("rv_sort_init", ptr(self.state[self.cur]), self.S, self.tmax, stream_ptr())
 
+    def set_projectors(self, projectors: Sequence[Optional[GroundProjector]]):
+        """One projector (or None) per camera stream: `update` then runs
+        rv_sort_update_cams, where stream s behaves as the reference's
+        SortTracker.update(dets, ts, projectors[s]) -- a stream whose
+        projector is None keeps reporting a matched track's last distance and
+        speed (sort_tracker.py:242-247), which the single-projector path
+        does not.  The table lives in device memory (`self.cams.dev`) and
+        keeps its address over later set_projectors / set_camera_projector
+        calls, so a recorded schedule follows them."""
+        projectors = list(projectors)
+        if len(projectors) != self.S:
+            raise ValueError(f"{len(projectors)} projectors for {self.S} camera streams")
+        if self.cams is None:
+            self.cams = CameraTable(projectors, self.device)
+        else:
+            self.cams.set_all(projectors)
+
+    def set_camera_projector(self, s: int, projector: Optional[GroundProjector]):
+        """Recalibrate camera stream s (None: remove its projector) with a
+        stream-ordered copy into the device table on the current stream; the
+        other cameras keep theirs.  Without a table yet, every other stream
+        starts from set_projector's projector."""
+        if not 0 <= int(s) < self.S:
+            raise IndexError(f"camera {s} outside [0, {self.S})")
+        if self.cams is None:
+            self.cams = CameraTable([self._single] * self.S, self.device)
+        self.cams.set(s, projector)
+
     def set_projector(self, projector: Optional[GroundProjector]):
+        """One projector for every stream (rv_sort_update); drops a
+        per-camera table."""
+        self.cams = None
+        self._single = projector
         if projector is None:
             self._H, self._origin = None, None
             self.params[4] = -1.0
@@ -69,6 +139,12 @@ class MultiStreamSort:
         if dets.shape[1] != self.dmax:
             raise ValueError(f"dets must be (S, {self.dmax}, 6)")
         st = self.state[0]
+        if self.cams is not None:
+            call("rv_sort_update_cams", ptr(st), ptr(st), self.S, self.tmax, ptr(dets),
+                 ptr(counts), self.dmax, ptr(ts), self.params.ctypes.data, ptr(self.cams.dev),
+                 ptr(self.ws), self.ws_bytes, ptr(self.out_id), ptr(self.out_dist),
+                 ptr(self.out_speed), stream_ptr())
+            return self.out_id, self.out_dist, self.out_speed
         Hp = self._H.ctypes.data if self._H is not None else None
         op = self._origin.ctypes.data if self._origin is not None else None
         call("rv_sort_update", ptr(st), ptr(st), self.S, self.tmax, ptr(dets), ptr(counts),
@@ -183,6 +259,20 @@ def project_boxes(H: torch.Tensor, boxes: torch.Tensor, origin: Optional[torch.T
     call("rv_homography_project_f64", ptr(H.contiguous()), ptr(boxes.contiguous()), n,
          ptr(origin) if origin is not None else None,
          -1.0 if max_distance is None else float(max_distance), ptr(xy), ptr(dist), stream_ptr())
+    return xy, dist
+
+
+def project_boxes_cams(cams: torch.Tensor, boxes: torch.Tensor, box_cam: torch.Tensor):
+    """project_boxes over a per-camera table: cams (S, 96) u8 device (a
+    CameraTable's `dev`), boxes (n,4) f32, box_cam (n,) int32 -- box i goes
+    through camera box_cam[i] -> (xy (n,2) f64, dist (n,) f64); NaN = None,
+    a disabled camera or a camera index outside [0, S)."""
+    n = boxes.shape[0]
+    dev = boxes.device
+    xy = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    dist = torch.empty(n, dtype=torch.float64, device=dev)
+    call("rv_homography_project_cams", ptr(cams), cams.shape[0], ptr(boxes.contiguous()),
+         ptr(box_cam.contiguous()), n, ptr(xy), ptr(dist), stream_ptr())
     return xy, dist
 
 
