@@ -684,16 +684,26 @@ int rv_fog_full_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int pit
 /* module 8's async pipeline).  One reader thread per source fills a ring of */
 /* pinned host slots from a file; frames are stamped with the wall-clock    */
 /* time they were read (capture.py:20).  Formats: YUV4MPEG2 4:2:0 (handed   */
-/* out as NV12), raw NV12, raw BGR.  No bitstream decoder / camera here.    */
+/* out as NV12), raw NV12, raw BGR, and Motion-JPEG (baseline JPEG images    */
+/* back to back; the reader thread entropy-decodes each into a coefficient   */
+/* record, see "Baseline JPEG" below).  No AVI / MP4 demuxer, no H.264, no   */
+/* live camera here.                                                        */
 /* ------------------------------------------------------------------------ */
 #define RV_CAP_Y4M 0
 #define RV_CAP_NV12 1
 #define RV_CAP_BGR 2
-/* W, H are read from the header for Y4M; nbuf in [2, 64] slots; loop != 0
+#define RV_CAP_MJPEG 3
+/* W, H are read from the header for Y4M and from the first image for MJPEG
+ * (every later image must keep its size and sampling: a change is a reader
+ * error that names the frame index); nbuf in [2, 64] slots; loop != 0
  * rewinds at end of file.  *handle owns a reader thread. */
 int rv_capture_open(const char* path, int fmt, int W, int H, int nbuf, int loop, void** handle);
-/* info[6] = {W, H, fmt, frame bytes (NV12: 3WH/2, BGR: 3WH), pinned, nbuf} */
+/* info[6] = {W, H, fmt, frame bytes (NV12: 3WH/2, BGR: 3WH, MJPEG: the
+ * coefficient record's size), pinned, nbuf} */
 int rv_capture_info(void* handle, int* info);
+/* MJPEG sources: info[14] = {sampling code, components, then the twelve
+ * values of rv_jpeg_record_layout for the source's records}. */
+int rv_capture_jpeg_info(void* handle, int64_t* info);
 /* Next frame in order (blocks until read): RV_OK with the slot's host pointer,
  * read time (s since the epoch) and frame index, or RV_EOF.  The slot stays
  * held until rv_capture_release. */
@@ -707,6 +717,48 @@ int rv_capture_release(void* handle, int slot);
 int rv_capture_upload_batch(void* const* handles, int S, uint8_t* dev, size_t dev_stride,
                             double* ts, int64_t* index, void* stream);
 int rv_capture_close(void* handle);
+
+/* ------------------------------------------------------------------------ */
+/* Baseline JPEG (what cv2.imdecode / VideoCapture do for JPEG and MJPG with */
+/* a default libjpeg build: "islow" IDCT, "fancy" chroma upsampling, 16-bit  */
+/* fixed-point YCbCr -> RGB; uint8 output bit for bit).  The host parses the  */
+/* markers and decodes the Huffman stream (csrc/jpeg_host.h), the device      */
+/* does the rest (csrc/jpeg.hip).  Supported: SOF0, 8-bit, one interleaved    */
+/* scan; three components with Y 1x1 / 2x1 / 2x2 and Cb, Cr 1x1 (4:4:4,        */
+/* 4:2:2, 4:2:0) or one component (grey, B = G = R); DRI / RSTn; the Annex K  */
+/* Huffman tables when an image has no DHT; APPn / COM skipped.  Progressive, */
+/* extended, lossless, arithmetic, 12-bit, 16-bit quant tables, 4 components, */
+/* other sampling factors and multi-scan files are RV_EINVAL with the cause   */
+/* in rv_last_error.                                                          */
+/*                                                                            */
+/* Between the two halves travels a fixed-size coefficient record:            */
+/*   int32[8]          {RV_JPEG_MAGIC, W, H, sampling code, components, 0..}  */
+/*   uint16[ncomp][64] quant tables, natural order (index 8 v + u)            */
+/*   per component     the MCU-padded block grid, row-major, each block 64    */
+/*                     int16 quantised coefficients in natural order          */
+/* rv_jpeg_record_layout gives the offsets: layout[12] = {record bytes,       */
+/* components, quant offset, coefficient offset x 3, blocks across x 3,       */
+/* blocks down x 3} (unused components 0).                                    */
+/* ------------------------------------------------------------------------ */
+#define RV_JPEG_MAGIC 0x46434a52
+#define RV_JPEG_444 0
+#define RV_JPEG_422 1
+#define RV_JPEG_420 2
+#define RV_JPEG_GRAY 3
+/* Host only (no device needed).  info[4] = {W, H, sampling code, components}
+ * of the image that starts at data[0]. */
+int rv_jpeg_probe(const uint8_t* data, size_t n, int* info);
+size_t rv_jpeg_record_bytes(int W, int H, int sampling); /* 0 for a bad size / code */
+int rv_jpeg_record_layout(int W, int H, int sampling, int64_t* layout);
+/* Entropy-decode one image into a record of at most `cap` bytes (host). */
+int rv_jpeg_decode_coef(const uint8_t* data, size_t n, uint8_t* record, size_t cap);
+/* S records of W x H images (device, record_stride bytes apart, 16-byte
+ * aligned; their sampling may differ) -> (S, H, W, 3) BGR u8.  One kernel on
+ * `stream`, no host reads.  W and H size the launch; a record whose header
+ * does not say W x H, or that does not fit its stride, leaves its frame
+ * unwritten. */
+int rv_jpeg_coef_to_bgr_u8(const uint8_t* records, size_t record_stride, int S, int W, int H,
+                           uint8_t* bgr, void* stream);
 
 /* --- Native launch schedule (csrc/sched.hip; no reference counterpart: the
  * reference runs its chain synchronously, main_preview.py:94-109).  A run of

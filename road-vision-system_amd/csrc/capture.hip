@@ -15,11 +15,16 @@
 // ring refills while the device works
 // and nothing blocks on a copy in flight.  No host callbacks are queued in
 // streams.  Frames travel as NV12 (1.5 B/pixel: what a decoder emits; the
-// device converts with rv_nv12_to_bgr_u8) or as raw BGR.
+// device converts with rv_nv12_to_bgr_u8), as raw BGR, or -- Motion-JPEG -- as
+// coefficient records: the reader thread parses and entropy-decodes each
+// image (jpeg_host.h) and the device does the IDCT, upsampling and colour
+// (rv_jpeg_coef_to_bgr_u8).
 //
 // Formats: YUV4MPEG2 (.y4m, 4:2:0 planar, converted to NV12 by the reader
-// thread: U/V interleave), raw NV12, raw BGR.  There is no bitstream decoder
-// in this image (no rocDecode), and no V4L2 camera: DESIGN.md §(f)4.
+// thread: U/V interleave), raw NV12, raw BGR, Motion-JPEG (baseline JPEG
+// images back to back; bytes between images are skipped).  There is no
+// AVI / MP4 demuxer, no H.264 (no rocDecode in this image) and no V4L2
+// camera: DESIGN.md §(f)4.
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -31,6 +36,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "jpeg_host.h"
 
 namespace rv {
 
@@ -52,6 +58,13 @@ struct Capture {
   bool loop = false, pinned = false;
   std::vector<CapSlot> slots;
   std::vector<uint8_t> uv;  // Y4M: one frame's U and V planes
+  // MJPEG: the first image's size and sampling (every image must keep them),
+  // and the window of the file the reader scans for the next image
+  rvjpeg::Info jinfo = {0, 0, 0, 0};
+  std::vector<uint8_t> buf;
+  size_t buf_lo = 0;
+  bool file_eof = false;
+  std::string errmsg;  // the reader thread's error, for the consumer's rv_last_error
   int head = 0, tail = 0;
   std::mutex m;
   std::condition_variable cv_fill, cv_take;
@@ -105,8 +118,65 @@ int parse_y4m_header(Capture* c) {
   return RV_OK;
 }
 
+constexpr size_t kMjpegChunk = 1 << 20;         // file bytes read at a time
+constexpr size_t kMjpegMaxImage = 256u << 20;  // an image longer than this is an error
+
+void rewind_window(Capture* c) {
+  c->buf.clear();
+  c->buf_lo = 0;
+  c->file_eof = false;
+}
+
+// The next image of an MJPEG file, [*img, *img + *len) inside c->buf: 1 = ok,
+// 0 = end of file (a truncated last image included), < 0 = error in `err`.
+int next_image(Capture* c, const uint8_t** img, size_t* len, char* err) {
+  for (;;) {
+    size_t b = 0, e = 0;
+    const uint8_t* p = c->buf.data() + c->buf_lo;
+    const size_t n = c->buf.size() - c->buf_lo;
+    const int rc = rvjpeg::frame_extent(p, n, &b, &e, err);
+    if (rc == rvjpeg::kOk) {
+      *img = p + b;
+      *len = e - b;
+      c->buf_lo += e;
+      return 1;
+    }
+    if (rc != rvjpeg::kTruncated) return RV_EINVAL;
+    c->buf_lo += b;  // bytes before the image's SOI are done with
+    if (c->file_eof) return 0;
+    if (c->buf.size() - c->buf_lo > kMjpegMaxImage) {
+      snprintf(err, rvjpeg::kErrLen, "JPEG: no end of image within %zu bytes", kMjpegMaxImage);
+      return RV_EINVAL;
+    }
+    c->buf.erase(c->buf.begin(), c->buf.begin() + (ptrdiff_t)c->buf_lo);
+    c->buf_lo = 0;
+    const size_t old = c->buf.size();
+    c->buf.resize(old + kMjpegChunk);
+    const size_t got = fread(c->buf.data() + old, 1, kMjpegChunk, c->f);
+    c->buf.resize(old + got);
+    if (got < kMjpegChunk) c->file_eof = true;
+  }
+}
+
+// One MJPEG image, entropy-decoded into the slot as a coefficient record.
+int read_mjpeg(Capture* c, uint8_t* dst) {
+  char err[rvjpeg::kErrLen] = "";
+  const uint8_t* img = nullptr;
+  size_t len = 0;
+  int rc = next_image(c, &img, &len, err);
+  if (rc == 1 && rvjpeg::decode(img, len, dst, c->frame_bytes, &c->jinfo, err) != rvjpeg::kOk)
+    rc = RV_EINVAL;
+  if (rc < 0) {
+    char msg[rvjpeg::kErrLen + 48];
+    snprintf(msg, sizeof(msg), "MJPEG frame %lld: %s", (long long)c->count, err);
+    c->errmsg = msg;  // read by the consumer after it sees eof (under the mutex)
+  }
+  return rc;
+}
+
 // One frame into `dst`: 1 = ok, 0 = end of file, < 0 = error.
 int read_frame(Capture* c, uint8_t* dst) {
+  if (c->fmt == RV_CAP_MJPEG) return read_mjpeg(c, dst);
   if (c->fmt == RV_CAP_Y4M) {
     char line[256];
     if (!fgets(line, sizeof(line), c->f)) return 0;
@@ -141,7 +211,10 @@ void reader_main(Capture* c) {
     int rc = read_frame(c, c->slots[i].p);
     if (rc == 0 && c->loop && c->count > 0) {
       clearerr(c->f);
-      if (fseek(c->f, c->data_start, SEEK_SET) == 0) rc = read_frame(c, c->slots[i].p);
+      if (fseek(c->f, c->data_start, SEEK_SET) == 0) {
+        rewind_window(c);
+        rc = read_frame(c, c->slots[i].p);
+      }
     }
     const double ts = wall_now();
     {
@@ -167,7 +240,10 @@ int take(Capture* c, int* slot) {
   std::unique_lock<std::mutex> lk(c->m);
   c->cv_take.wait(lk, [&] { return c->slots[c->tail].state == 1 || c->eof; });
   CapSlot& s = c->slots[c->tail];
-  if (s.state != 1) return c->err != RV_OK ? c->err : RV_EOF;
+  if (s.state != 1) {
+    if (c->err != RV_OK && !c->errmsg.empty()) set_error("%s", c->errmsg.c_str());
+    return c->err != RV_OK ? c->err : RV_EOF;
+  }
   s.state = 2;
   *slot = c->tail;
   c->tail = (c->tail + 1) % (int)c->slots.size();
@@ -243,7 +319,8 @@ int take_for_upload(Capture* c, int* slot) {
 extern "C" int rv_capture_open(const char* path, int fmt, int W, int H, int nbuf, int loop,
                                void** handle) {
   RV_CHECK_ARG(path != nullptr && handle != nullptr, "null pointer");
-  RV_CHECK_ARG(fmt == RV_CAP_Y4M || fmt == RV_CAP_NV12 || fmt == RV_CAP_BGR, "format %d", fmt);
+  RV_CHECK_ARG(fmt == RV_CAP_Y4M || fmt == RV_CAP_NV12 || fmt == RV_CAP_BGR || fmt == RV_CAP_MJPEG,
+               "format %d", fmt);
   RV_CHECK_ARG(nbuf >= 2 && nbuf <= 64, "nbuf %d out of [2, 64]", nbuf);
   *handle = nullptr;
   Capture* c = new Capture();
@@ -256,8 +333,28 @@ extern "C" int rv_capture_open(const char* path, int fmt, int W, int H, int nbuf
     return RV_EINVAL;
   }
   int rc = RV_OK;
+  rvjpeg::Layout jlay;
   if (fmt == RV_CAP_Y4M) {
     rc = parse_y4m_header(c);
+  } else if (fmt == RV_CAP_MJPEG) {  // size and sampling come from the first image
+    char err[rvjpeg::kErrLen] = "";
+    const uint8_t* img = nullptr;
+    size_t len = 0;
+    rc = next_image(c, &img, &len, err);
+    if (rc == 1 && rvjpeg::probe(img, len, &c->jinfo, err) != rvjpeg::kOk) rc = RV_EINVAL;
+    if (rc == 0) snprintf(err, sizeof(err), "no complete JPEG image");
+    if (rc == 1 && rvjpeg::layout(c->jinfo.W, c->jinfo.H, c->jinfo.sampling, &jlay) != rvjpeg::kOk)
+      rc = RV_EINVAL;
+    if (rc != 1) {
+      set_error("%s: %s", path, err);
+      rc = RV_EINVAL;
+    } else {
+      rc = fseek(c->f, 0, SEEK_SET) == 0 ? RV_OK : RV_EINVAL;
+      if (rc != RV_OK) set_error("%s: cannot rewind", path);
+      rewind_window(c);
+      c->W = c->jinfo.W;
+      c->H = c->jinfo.H;
+    }
   } else if (W <= 0 || H <= 0 || (fmt == RV_CAP_NV12 && (W % 2 || H % 2))) {
     set_error("raw frames need a positive size (NV12: even) %dx%d", W, H);
     rc = RV_EINVAL;
@@ -273,6 +370,7 @@ extern "C" int rv_capture_open(const char* path, int fmt, int W, int H, int nbuf
   c->data_start = ftell(c->f);
   const size_t px = (size_t)c->W * c->H;
   c->frame_bytes = fmt == RV_CAP_BGR ? 3 * px : px + px / 2;
+  if (fmt == RV_CAP_MJPEG) c->frame_bytes = jlay.record_bytes;
   if (fmt == RV_CAP_Y4M) c->uv.resize(px / 2);
   c->slots.resize(nbuf);
   int dev_count = 0;
@@ -312,6 +410,15 @@ extern "C" int rv_capture_info(void* handle, int* info) {
   info[4] = c->slots[0].pinned ? 1 : 0;
   info[5] = (int)c->slots.size();
   return RV_OK;
+}
+
+extern "C" int rv_capture_jpeg_info(void* handle, int64_t* info) {
+  RV_CHECK_ARG(handle != nullptr && info != nullptr, "null pointer");
+  Capture* c = static_cast<Capture*>(handle);
+  RV_CHECK_ARG(c->fmt == RV_CAP_MJPEG, "not an MJPEG source (format %d)", c->fmt);
+  info[0] = c->jinfo.sampling;
+  info[1] = c->jinfo.ncomp;
+  return rv_jpeg_record_layout(c->W, c->H, c->jinfo.sampling, info + 2);
 }
 
 extern "C" int rv_capture_next(void* handle, uint8_t** frame, double* ts, int64_t* index,

@@ -82,6 +82,14 @@ _SIGS = {
     "rv_capture_upload_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                         c_void_p]),
     "rv_capture_close": (c_int, [c_void_p]),
+    "rv_capture_jpeg_info": (c_int, [c_void_p, c_void_p]),
+    # baseline JPEG: host probe / entropy decode, device IDCT + colour
+    "rv_jpeg_probe": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "rv_jpeg_record_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rv_jpeg_record_layout": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "rv_jpeg_decode_coef": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t]),
+    "rv_jpeg_coef_to_bgr_u8": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
+                                       c_void_p]),
     "rv_fog_full_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rv_fog_full_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -101,6 +101,30 @@ def nv12_to_bgr(nv12: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
     return out
 
 
+def jpeg_to_bgr(records: torch.Tensor, W: int, H: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """JPEG coefficient records (S, record bytes) u8 on device (what
+    rv_jpeg_decode_coef and the MJPEG readers produce for W x H images; the
+    records' sampling and quant tables may differ) -> (S, H, W, 3) BGR, bit
+    for bit libjpeg's default decode.  A 1-D record gives one (H, W, 3) frame."""
+    if records.dim() == 1:
+        return jpeg_to_bgr(records.unsqueeze(0), W, H,
+                           None if out is None else out.unsqueeze(0))[0]
+    if records.dim() != 2 or records.dtype != torch.uint8 or not records.is_cuda:
+        raise ValueError("expected JPEG coefficient records, uint8 (S, bytes), on the GPU")
+    S = records.shape[0]
+    stride = records.stride(0) if S > 1 else records.shape[1] // 16 * 16
+    if records.stride(1) != 1 or stride % 16 or records.data_ptr() % 16:
+        raise ValueError("records must be rows of bytes, 16-byte aligned with a 16-byte stride")
+    if out is None:
+        out = torch.empty((S, H, W, 3), dtype=torch.uint8, device=records.device)
+    elif out.shape != (S, H, W, 3) or not out.is_contiguous() or out.dtype != torch.uint8:
+        raise ValueError("out must be a contiguous (S, H, W, 3) uint8 tensor")
+    call("rv_jpeg_coef_to_bgr_u8", ptr(records), stride, S, int(W), int(H), ptr(out),
+         stream_ptr())
+    return out
+
+
 def median(frames: torch.Tensor, k: int = 3, out: Optional[torch.Tensor] = None):
     x, B, H, W, pitch = _frames(frames)
     out = _like(x, out)
