@@ -385,7 +385,7 @@ __global__ __launch_bounds__(512) void c2f_chain_kernel(C2fArgs a) {
       uint16_t* dst = a.out + ((size_t)(b * a.H + gy) * a.W + gx) * a.out_cs + a.out_co;
       // fragment pairs (m, m+1) as 16-B stores: after one v_permlane16_swap
       // per packed dword quad q holds channels 8 (q >> 1) .. +7 of fragment
-      // m + (q & 1) (conv.hip epilogue_fast); all quads of a pixel share
+      // m + (q & 1) (conv_kernels.h epilogue_fast); all quads of a pixel share
       // the bounds test above
 #pragma unroll
       for (int m = 0; m < MR2; m += 2) {

@@ -1,5 +1,6 @@
-// Internal interface of the YOLOv8 conv / pool / head kernels (conv.hip,
-// sppf.hip, detect.hip, stem.hip, c2f.hip) used by the model plan (yolo.hip).
+// Internal interface of the YOLOv8 conv / pool / head kernels (conv.hip and
+// its kernels' conv_patch.hip / conv_direct.hip / conv_generic.hip, sppf.hip,
+// detect.hip, stem.hip, c2f.hip) used by the model plan (yolo.hip).
 // Activations are NHWC bf16 (raw uint16 bits); a "view" is (base pointer,
 // channel stride of the buffer, channel offset), so concatenation is free:
 // producers write into a slice of a wider buffer and consumers read a slice.

@@ -1,4 +1,4 @@
-// Helpers shared by the conv kernels (conv.hip), the stem / conv0 kernels
+// Helpers shared by the conv kernels (conv_*.hip), the stem / conv0 kernels
 // (stem.hip), the SPPF pool (sppf.hip) and the Detect decode (detect.hip):
 // operand vector types, bf16 packing, SiLU, the raw buffer-resource
 // constants, the fp8 encoder and the device's CU count.

@@ -1,4 +1,4 @@
-"""conv 0's integer form (yolo_def.hip pack_conv0q, conv.hip conv0_kernel /
+"""conv 0's integer form (yolo_def.hip pack_conv0q, stem.hip conv0_kernel /
 stem_kernel): the packer's balanced base-256 i8 digits reconstruct integers
 Q = round(V / s) of V = w[rgb][ky][kx] / 255 at 2^-23 of each channel's
 largest |V|; the kernel's per-digit sums (accumulators started at

@@ -50,7 +50,7 @@ RV_EINVAL = -1000  # include/rvhip.h
 PATTERN = 0x5AA5  # bf16 bits of every output element the call must not write
 MIN_ELEMS = 20000
 TILES = [(8, 2), (8, 1), (5, 2), (5, 1), (4, 4), (4, 2), (4, 1), (2, 4), (2, 2), (2, 1), (1, 4),
-         (1, 2), (1, 1)]  # kTiles of csrc/conv.hip
+         (1, 2), (1, 1)]  # RV_TILES of csrc/conv_kernels.h
 CONFIGS = [(mr, nr, 1, resw, persist, kind) for (mr, nr) in TILES for kind in (0, 1, 2)
            for resw in (0, 1) for persist in (0, 1)]
 
