@@ -760,6 +760,101 @@ int rv_jpeg_decode_coef(const uint8_t* data, size_t n, uint8_t* record, size_t c
 int rv_jpeg_coef_to_bgr_u8(const uint8_t* records, size_t record_stride, int S, int W, int H,
                            uint8_t* bgr, void* stream);
 
+/* --- The way back: a baseline JPEG encoder whose output equals, byte for
+ * byte, what libjpeg writes with its default settings and one restart
+ * segment per MCU row (Pillow: save(quality=q, subsampling=s,
+ * restart_marker_rows=1); cv2.imwrite's arithmetic).  16-bit fixed-point
+ * RGB -> YCbCr, right edge replicated, h2v1 / h2v2 box downsampling with
+ * libjpeg's alternating bias, the bottom edge padded per row group and then
+ * per downsampled plane, "islow" forward DCT, quant tables of
+ * jpeg_quality_scaling, the Annex K Huffman tables, JFIF 1.01 APP0.  Markers
+ * in order: SOI, APP0, DQT, DQT, SOF0, DHT x 4, DRI, SOS, segments separated
+ * by RSTm, EOI.  Colour input only: RV_JPEG_GRAY is RV_EINVAL in the device
+ * entries.  The host half (csrc/jpeg_host.h) needs no device. */
+/* Quant tables of `quality` (1..100), uint16[64] each, natural order. */
+int rv_jpeg_quant_tables(int quality, uint16_t* luma, uint16_t* chroma);
+/* SOI .. SOS of a W x H image (at most 640 bytes) -> out[0, *n); DRI only
+ * when restart_interval_mcus > 0.  Sampling may be RV_JPEG_GRAY here. */
+int rv_jpeg_write_header(int W, int H, int sampling, int quality, int restart_interval_mcus,
+                         uint8_t* out, size_t cap, size_t* n);
+/* Host: a coefficient record -> a complete image in out[0, *n), the inverse
+ * of rv_jpeg_decode_coef for images that use the Annex K Huffman tables.
+ * The quant tables come from the record; grey records are supported;
+ * restart_interval_mcus = 0 writes no DRI.  RV_EINVAL when the image does
+ * not fit `cap` or a value has no baseline code. */
+int rv_jpeg_encode_coef(const uint8_t* record, size_t record_bytes, int restart_interval_mcus,
+                        uint8_t* out, size_t cap, size_t* n);
+
+/* A device stream is a 16-byte header, uint32[4] = {RV_JPEG_STREAM_MAGIC,
+ * image bytes, flags, restart segments}, followed by the image.  "image
+ * bytes" is the size the image needs, whether or not it fitted. */
+#define RV_JPEG_STREAM_MAGIC 0x534a5652 /* "RVJS" */
+#define RV_JPEG_STREAM_HEADER_BYTES 16
+#define RV_JPEG_STREAM_OVERFLOW 1   /* header + image > capacity: image cut at capacity */
+#define RV_JPEG_STREAM_BAD_RECORD 2 /* the record is not a W x H record of this sampling */
+/* Worst-case stream size (header included, rounded up to 16), 0 for a bad
+ * size or code: 16 + 640 (file header) + blocks x 416 + MCU rows x 4 + 2.  A
+ * block takes at most 1660 bits = 208 bytes (DC: 11-bit code + 11 value bits;
+ * 63 AC coefficients x (16-bit code + 10 value bits)), every byte of which
+ * may be 0xFF and stuffed; a segment adds its padded last byte, stuffed, and
+ * its RSTm. */
+size_t rv_jpeg_stream_bound(int W, int H, int sampling);
+/* (S, H, W, 3) BGR u8 frames (device, contiguous) -> S coefficient records in
+ * the layout above (three components, quant tables of `quality`),
+ * record_stride bytes apart, 16-byte aligned.  rv_jpeg_coef_to_bgr_u8 and the
+ * host entries read them unchanged.  One kernel on `stream`, no host reads. */
+int rv_jpeg_bgr_to_coef_u8(const uint8_t* bgr, int S, int H, int W, int sampling, int quality,
+                           uint8_t* records, size_t record_stride, void* stream);
+size_t rv_jpeg_stream_ws_bytes(int S, int W, int H, int sampling);
+/* S device records of W x H colour images with this sampling -> S streams,
+ * stream_stride bytes apart (4-byte aligned).  `header` (host, copied during
+ * the call) is the SOI .. SOS prefix every image starts with, from
+ * rv_jpeg_write_header with restart_interval_mcus = MCUs per MCU row; its
+ * quant tables must be the records'.  Every MCU row is entropy-coded as its
+ * own restart segment and the segments are compacted on the device.  No more
+ * than `capacity` (<= stream_stride) bytes of a stream are written: a frame
+ * that does not fit gets RV_JPEG_STREAM_OVERFLOW and the bytes that do fit.
+ * `ws` (device, 16-byte aligned, rv_jpeg_stream_ws_bytes) is scratch.  Two
+ * kernels on `stream`, no host reads. */
+int rv_jpeg_coef_to_stream(const uint8_t* records, size_t record_stride, int S, int W, int H,
+                           int sampling, const uint8_t* header, size_t header_bytes, uint8_t* ws,
+                           size_t ws_bytes, uint8_t* streams, size_t stream_stride,
+                           size_t capacity, void* stream);
+size_t rv_jpeg_encode_ws_bytes(int S, int W, int H, int sampling);
+/* Frames -> streams: the two entries above over `ws` (rv_jpeg_encode_ws_bytes:
+ * the records and the entropy scratch). */
+int rv_jpeg_encode_bgr_u8(const uint8_t* bgr, int S, int H, int W, int sampling, int quality,
+                          uint8_t* ws, size_t ws_bytes, uint8_t* streams, size_t stream_stride,
+                          size_t capacity, void* stream);
+
+/* --- Motion-JPEG file sink (csrc/sink.hip; the reference's writer.write,
+ * main_preview.py:130,137), the counterpart of rv_capture_*: one writer
+ * thread per file over a ring of nbuf (2..64) pinned slots of `capacity`
+ * bytes, the capacity the streams were encoded with.  The file holds the
+ * images back to back, which RV_CAP_MJPEG reads; there is no MP4 / AVI muxer,
+ * and no timing is stored. */
+int rv_sink_open(const char* path, int nbuf, size_t capacity, void** handle);
+/* Stream s of `streams` (device, rv_jpeg_encode_bgr_u8's output, stream_stride
+ * >= capacity bytes apart) is appended to file handles[s].  The call records
+ * an event on `stream` and returns; it never makes `stream` wait.  The writer
+ * waits for the event, copies the stream header and then the image's bytes
+ * rounded up to 4 KiB on a stream of its own, and writes the image.  Frames
+ * reach the file in submission order.  A full ring blocks the caller.  The
+ * device memory of a batch must stay unchanged until nbuf later calls have
+ * returned (nbuf + 1 buffers in rotation do).  A frame that overflowed, a
+ * stream without the magic and an I/O error are counted, nothing is written
+ * for that frame, and the next call (and rv_sink_flush / rv_sink_close)
+ * returns RV_EINVAL with the file and frame in rv_last_error. */
+int rv_sink_write_batch(void* const* handles, int S, const uint8_t* streams, size_t stream_stride,
+                        void* stream);
+/* stats[8] = {frames submitted, frames written, bytes written, bytes copied
+ * from the device, frames overflowed, other failed frames, nbuf, capacity} */
+int rv_sink_stats(void* handle, int64_t* stats);
+/* Wait until every submitted frame is in the file and flush it. */
+int rv_sink_flush(void* handle);
+/* Write what is queued, flush, close the file, free the ring. */
+int rv_sink_close(void* handle);
+
 /* --- Native launch schedule (csrc/sched.hip; no reference counterpart: the
  * reference runs its chain synchronously, main_preview.py:94-109).  A run of
  * K pipelined steps recorded once as a list of stream-ordered calls of this

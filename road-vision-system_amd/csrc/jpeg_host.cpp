@@ -1,5 +1,6 @@
-// Baseline JPEG marker parser and Huffman decoder: see jpeg_host.h.
+// Baseline JPEG marker parser, Huffman decoder and Huffman coder: see jpeg_host.h.
 #include "jpeg_host.h"
+#include "jpeg_tables.h"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -8,42 +9,6 @@
 namespace rvjpeg {
 
 namespace {
-
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
-                             12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-                             35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-                             58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// T.81 Annex K.3 typical Huffman tables: counts per code length 1..16, symbols
-const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
-const uint8_t kAcLumaVals[162] = {
-    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
-    0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0,
-    0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
-    0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49,
-    0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
-    0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
-    0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7,
-    0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5,
-    0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
-    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
-    0xf9, 0xfa};
-const uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
-const uint8_t kAcChromaVals[162] = {
-    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71,
-    0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0,
-    0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
-    0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68,
-    0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
-    0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5,
-    0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
-    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
-    0xf9, 0xfa};
 
 int fail(char* err, int code, const char* fmt, ...) {
   if (err) {
@@ -525,6 +490,237 @@ int decode(const uint8_t* data, size_t n, uint8_t* record, size_t cap, const Inf
   }
   delete f;
   return rc;
+}
+
+// ---- encoder half ---------------------------------------------------------
+
+void quant_tables(int quality, uint16_t luma[64], uint16_t chroma[64]) {
+  const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+  for (int i = 0; i < 64; ++i) {
+    const int l = (kQuantLuma[i] * scale + 50) / 100, c = (kQuantChroma[i] * scale + 50) / 100;
+    luma[i] = (uint16_t)(l < 1 ? 1 : (l > 255 ? 255 : l));
+    chroma[i] = (uint16_t)(c < 1 ? 1 : (c > 255 ? 255 : c));
+  }
+}
+
+size_t image_bound(int W, int H, int sampling) {
+  Layout l;
+  if (layout(W, H, sampling, &l) != kOk) return 0;
+  size_t blocks = 0;
+  for (int c = 0; c < l.ncomp; ++c) blocks += (size_t)l.blocks_w[c] * l.blocks_h[c];
+  return (size_t)kFileHeaderMax + blocks * (2 * ((kBlockBitsMax + 7) / 8)) +
+         (size_t)l.blocks_h[l.ncomp - 1] * 4 + 2;
+}
+
+namespace {
+
+constexpr HuffEnc kHuffEnc = make_huff_enc();
+
+// Bounded byte sink: counts every byte, stores those that fit.
+struct Out {
+  uint8_t* o;
+  size_t cap, n = 0;
+  inline void byte(unsigned b) {
+    if (n < cap) o[n] = (uint8_t)b;
+    ++n;
+  }
+  inline void be16(unsigned v) {
+    byte(v >> 8);
+    byte(v & 255);
+  }
+  inline void marker(unsigned m, unsigned len) {
+    byte(0xFF);
+    byte(m);
+    be16(len);
+  }
+};
+
+// Entropy-coded bits, MSB first, 0x00 stuffed after every 0xFF byte.
+struct PutBits {
+  Out* out;
+  uint64_t acc = 0;
+  int cnt = 0;
+  inline void put(uint32_t v, int k) {  // k <= 32, v < 2^k
+    acc = (acc << k) | v;
+    cnt += k;
+    while (cnt >= 8) {
+      const unsigned b = (unsigned)(acc >> (cnt - 8)) & 255;
+      out->byte(b);
+      if (b == 0xFF) out->byte(0);
+      cnt -= 8;
+    }
+  }
+  inline void align() {  // pad the last byte with 1-bits
+    if (cnt) put((1u << (8 - cnt)) - 1, 8 - cnt);
+  }
+};
+
+inline int category(int a) {  // bits of |v|
+  int s = 0;
+  while (a) {
+    ++s;
+    a >>= 1;
+  }
+  return s;
+}
+
+void write_dht(Out& o, int tc_th, const uint8_t* counts, const uint8_t* syms, int nsym) {
+  o.marker(0xC4, 2 + 1 + 16 + nsym);
+  o.byte(tc_th);
+  for (int i = 0; i < 16; ++i) o.byte(counts[i]);
+  for (int i = 0; i < nsym; ++i) o.byte(syms[i]);
+}
+
+}  // namespace
+
+int write_header(int W, int H, int sampling, const uint16_t* luma, const uint16_t* chroma,
+                 int restart_interval_mcus, uint8_t* out, size_t cap, size_t* n, char* err) {
+  Layout lay;
+  if (!out || !n || !luma || (sampling != 3 && !chroma))
+    return fail(err, kInvalid, "JPEG: null pointer");
+  if (layout(W, H, sampling, &lay) != kOk)
+    return fail(err, kInvalid, "JPEG: size %dx%d, sampling code %d", W, H, sampling);
+  if (restart_interval_mcus < 0 || restart_interval_mcus > 65535)
+    return fail(err, kInvalid, "JPEG: restart interval %d", restart_interval_mcus);
+  const int nc = lay.ncomp;
+  for (int t = 0; t < (nc == 1 ? 1 : 2); ++t)
+    for (int i = 0; i < 64; ++i) {
+      const int v = (t ? chroma : luma)[i];
+      if (v < 1 || v > 255)
+        return fail(err, kInvalid, "JPEG: quant table entry %d is not baseline (1..255)", v);
+    }
+  Out o{out, cap};
+  o.byte(0xFF);
+  o.byte(0xD8);
+  o.marker(0xE0, 16);  // JFIF 1.01, no units, density 1 x 1, no thumbnail
+  const uint8_t jfif[12] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1};
+  for (int i = 0; i < 12; ++i) o.byte(jfif[i]);
+  o.byte(0);
+  o.byte(0);
+  for (int t = 0; t < (nc == 1 ? 1 : 2); ++t) {
+    o.marker(0xDB, 67);
+    o.byte(t);
+    for (int i = 0; i < 64; ++i) o.byte((t ? chroma : luma)[kZigzag[i]]);
+  }
+  o.marker(0xC0, 8 + 3 * nc);
+  o.byte(8);
+  o.be16(H);
+  o.be16(W);
+  o.byte(nc);
+  const int hs = sampling == 1 || sampling == 2 ? 2 : 1, vs = sampling == 2 ? 2 : 1;
+  for (int c = 0; c < nc; ++c) {
+    o.byte(c + 1);
+    o.byte(c == 0 ? (hs << 4) | vs : 0x11);
+    o.byte(c == 0 ? 0 : 1);
+  }
+  write_dht(o, 0x00, kDcLumaBits, kDcVals, 12);
+  write_dht(o, 0x10, kAcLumaBits, kAcLumaVals, 162);
+  if (nc == 3) {
+    write_dht(o, 0x01, kDcChromaBits, kDcVals, 12);
+    write_dht(o, 0x11, kAcChromaBits, kAcChromaVals, 162);
+  }
+  if (restart_interval_mcus) {
+    o.marker(0xDD, 4);
+    o.be16(restart_interval_mcus);
+  }
+  o.marker(0xDA, 6 + 2 * nc);
+  o.byte(nc);
+  for (int c = 0; c < nc; ++c) {
+    o.byte(c + 1);
+    o.byte(c == 0 ? 0x00 : 0x11);
+  }
+  o.byte(0);
+  o.byte(63);
+  o.byte(0);
+  *n = o.n;
+  if (o.n > cap) return fail(err, kInvalid, "JPEG: header needs %zu bytes, %zu given", o.n, cap);
+  return kOk;
+}
+
+int encode(const uint8_t* record, size_t record_bytes, int restart_interval_mcus, uint8_t* out,
+           size_t cap, size_t* n, char* err) {
+  if (!record || !out || !n) return fail(err, kInvalid, "JPEG: null pointer");
+  if (record_bytes < (size_t)kHeaderBytes) return fail(err, kInvalid, "JPEG: record too short");
+  int32_t hdr[8];
+  memcpy(hdr, record, sizeof(hdr));
+  Layout lay;
+  if ((uint32_t)hdr[0] != kMagic || layout(hdr[1], hdr[2], hdr[3], &lay) != kOk ||
+      hdr[4] != lay.ncomp)
+    return fail(err, kInvalid, "JPEG: not a coefficient record");
+  if (record_bytes < lay.record_bytes)
+    return fail(err, kInvalid, "JPEG: record needs %zu bytes, %zu given", lay.record_bytes,
+                record_bytes);
+  const int nc = lay.ncomp, sampling = hdr[3];
+  uint16_t qt[3][64];
+  memcpy(qt, record + lay.qt_off, (size_t)nc * 128);
+  if (nc == 3 && memcmp(qt[1], qt[2], 128) != 0)
+    return fail(err, kInvalid, "JPEG: Cb and Cr use different quant tables");
+  size_t hn = 0;
+  int rc = write_header(hdr[1], hdr[2], sampling, qt[0], qt[nc == 3 ? 1 : 0],
+                        restart_interval_mcus, out, cap, &hn, err);
+  if (rc != kOk) return rc;
+  Out o{out, cap};
+  o.n = hn;
+  PutBits pb{&o};
+  const int hs = sampling == 1 || sampling == 2 ? 2 : 1, vs = sampling == 2 ? 2 : 1;
+  const int mx = lay.blocks_w[0] / hs, my = lay.blocks_h[0] / vs;
+  int pred[3] = {0, 0, 0};
+  long mcu = 0;
+  int rst = 0;
+  for (int yy = 0; yy < my; ++yy) {
+    for (int xx = 0; xx < mx; ++xx, ++mcu) {
+      if (restart_interval_mcus && mcu && mcu % restart_interval_mcus == 0) {
+        pb.align();
+        o.byte(0xFF);
+        o.byte(0xD0 + (rst++ & 7));
+        pred[0] = pred[1] = pred[2] = 0;
+      }
+      for (int c = 0; c < nc; ++c) {
+        const int ch = c == 0 ? hs : 1, cv = c == 0 ? vs : 1, t = c == 0 ? 0 : 1;
+        for (int j = 0; j < ch * cv; ++j) {
+          const size_t bi = (size_t)(yy * cv + j / ch) * lay.blocks_w[c] + xx * ch + j % ch;
+          int16_t blk[64];
+          memcpy(blk, record + lay.coef_off[c] + bi * 128, 128);
+          const int diff = blk[0] - pred[c];
+          pred[c] = blk[0];
+          int s = category(diff < 0 ? -diff : diff);
+          if (s > 11) return fail(err, kInvalid, "JPEG: DC difference %d has no baseline code", diff);
+          uint32_t e = kHuffEnc.dc[t][s];
+          pb.put(e & 0xFFFF, (int)(e >> 16));
+          if (s) pb.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
+          int run = 0;
+          for (int k = 1; k < 64; ++k) {
+            const int v = blk[kZigzag[k]];
+            if (v == 0) {
+              ++run;
+              continue;
+            }
+            for (; run >= 16; run -= 16) {
+              e = kHuffEnc.ac[t][0xF0];
+              pb.put(e & 0xFFFF, (int)(e >> 16));
+            }
+            s = category(v < 0 ? -v : v);
+            if (s > 10) return fail(err, kInvalid, "JPEG: coefficient %d has no baseline code", v);
+            e = kHuffEnc.ac[t][(run << 4) | s];
+            pb.put(e & 0xFFFF, (int)(e >> 16));
+            pb.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
+            run = 0;
+          }
+          if (run) {
+            e = kHuffEnc.ac[t][0];
+            pb.put(e & 0xFFFF, (int)(e >> 16));
+          }
+        }
+      }
+    }
+  }
+  pb.align();
+  o.byte(0xFF);
+  o.byte(0xD9);
+  *n = o.n;
+  if (o.n > cap) return fail(err, kInvalid, "JPEG: image needs %zu bytes, %zu given", o.n, cap);
+  return kOk;
 }
 
 }  // namespace rvjpeg

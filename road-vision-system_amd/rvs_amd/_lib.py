@@ -90,6 +90,27 @@ _SIGS = {
     "rv_jpeg_decode_coef": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t]),
     "rv_jpeg_coef_to_bgr_u8": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
                                        c_void_p]),
+    # baseline JPEG encoder: host tables / header / Huffman coder, device DCT + entropy coding
+    "rv_jpeg_quant_tables": (c_int, [c_int, c_void_p, c_void_p]),
+    "rv_jpeg_write_header": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                     c_void_p]),
+    "rv_jpeg_encode_coef": (c_int, [c_void_p, c_size_t, c_int, c_void_p, c_size_t, c_void_p]),
+    "rv_jpeg_stream_bound": (c_size_t, [c_int, c_int, c_int]),
+    "rv_jpeg_bgr_to_coef_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_size_t, c_void_p]),
+    "rv_jpeg_stream_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rv_jpeg_coef_to_stream": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t,
+                                       c_void_p]),
+    "rv_jpeg_encode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rv_jpeg_encode_bgr_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_size_t, c_void_p, c_size_t, c_size_t, c_void_p]),
+    # Motion-JPEG file sink
+    "rv_sink_open": (c_int, [c_char_p, c_int, c_size_t, c_void_p]),
+    "rv_sink_write_batch": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "rv_sink_stats": (c_int, [c_void_p, c_void_p]),
+    "rv_sink_flush": (c_int, [c_void_p]),
+    "rv_sink_close": (c_int, [c_void_p]),
     "rv_fog_full_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rv_fog_full_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -24,6 +24,7 @@ from .detect.weights import detector_weights, names_from_config, variant_of
 from .detect.yolo_hip import YoloEngine
 from .geometry import GroundProjector, build_camera_projectors, build_projector
 from .handback import Record, handback
+from .io_video.sink import MultiStreamSink, record_settings
 from .preprocess import PreprocessPipeline
 from .track.sort_hip import CameraTable, MultiStreamSort
 
@@ -49,6 +50,10 @@ class RoadVisionEngine:
         cfg = cfg if cfg is not None else load_config()
         self.cfg = cfg
         self.S = int(n_streams)
+        # preview.record: checked before anything is built (a wrong container
+        # or a shared path is a configuration error, not a feature to drop)
+        record_cfg = record_settings(cfg, self.S)
+        self.recorder = None
         self.pair = max(1, int(pair))
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         self.device = torch.device(device)
@@ -129,6 +134,19 @@ class RoadVisionEngine:
         # default chain: CLAHE + median + the detector's LetterBox in one pass
         self.fused_letterbox = self.detector is not None and \
             self.pipeline.letterbox_fusable(self.H, self.W, self.detector.geo)
+        if record_cfg is not None:
+            # main_preview.py:130,137 (writer.write): every stream's proc frames
+            # as a Motion-JPEG file, encoded on a side stream of step()
+            self.recorder = MultiStreamSink(record_cfg["paths"], (self.H, self.W),
+                                            quality=record_cfg["quality"],
+                                            sampling=record_cfg["sampling"], device=self.device)
+
+    def _record_proc(self, proc: torch.Tensor) -> None:
+        """preview.record: queue this step's proc frames for the files.  The
+        encode waits (on its own stream) for an event recorded here, behind
+        the preprocess; the current stream goes on with the detector."""
+        if self.recorder is not None:
+            self.recorder.write(proc)
 
     def _need_detector(self, what: str) -> None:
         if self.detector is None:
@@ -193,6 +211,7 @@ class RoadVisionEngine:
     def detect_stage(self, frames: torch.Tensor, slot: int = 0) -> torch.Tensor:
         self._need_detector("detect_stage")
         proc, lb = self.preprocess_stage(frames)
+        self._record_proc(proc)
         self.yolo_stage(lb, slot)
         return proc
 
@@ -262,6 +281,8 @@ class RoadVisionEngine:
         self._need_detector("step_unit")
         S = self.S
         procs = [self.preprocess_stage(f, 0, h * S)[0] for h, f in enumerate(frames_list)]
+        for p in procs:
+            self._record_proc(p)
         self.yolo_stage(self.detector.lb[0][:S * len(frames_list)], 0)
         outs = self.track_pair_stage(ts_list, 0, records)
         for o, p in zip(outs, procs):
@@ -277,6 +298,7 @@ class RoadVisionEngine:
         preprocess runs and every stream's list is empty (main_preview.py:97-99)."""
         if self.detector is None:
             proc, _ = self.preprocess_stage(frames)
+            self._record_proc(proc)
             return {"proc": proc, "no_detector": True}
         proc = self.detect_stage(frames, 0)
         out = self.track_stage(ts, 0, self.record if record is None else record)
@@ -346,8 +368,13 @@ class RoadVisionEngine:
         return self.tracker.stats()
 
     def close(self):
+        """Also finishes a recording: queued frames are written, the files are
+        flushed, and a frame that could not be written is raised here."""
         if self.detector is not None:
             self.detector.close()
+        if self.recorder is not None:
+            recorder, self.recorder = self.recorder, None
+            recorder.close()
 
 
 class _UntrackedMetrics:

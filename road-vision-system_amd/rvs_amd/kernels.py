@@ -125,6 +125,106 @@ def jpeg_to_bgr(records: torch.Tensor, W: int, H: int,
     return out
 
 
+JPEG_SAMPLING = {"444": 0, "422": 1, "420": 2}
+JPEG_STREAM_MAGIC, JPEG_STREAM_HEADER_BYTES = 0x534A5652, 16
+JPEG_STREAM_OVERFLOW, JPEG_STREAM_BAD_RECORD = 1, 2
+
+
+def jpeg_sampling_code(sampling) -> int:
+    """"444" / "422" / "420" (or the RV_JPEG_* code itself) -> RV_JPEG_* code."""
+    if isinstance(sampling, str):
+        if sampling not in JPEG_SAMPLING:
+            raise ValueError(f"JPEG sampling {sampling!r}: expected '444', '422' or '420'")
+        return JPEG_SAMPLING[sampling]
+    return int(sampling)
+
+
+def jpeg_stream_bound(W: int, H: int, sampling) -> int:
+    """Worst-case bytes of one encoded stream (rv_jpeg_stream_bound)."""
+    n = int(_lib.load().rv_jpeg_stream_bound(int(W), int(H), jpeg_sampling_code(sampling)))
+    if n == 0:
+        raise ValueError(f"no JPEG stream bound for {W}x{H}, sampling {sampling!r}")
+    return n
+
+
+def jpeg_file_header(W: int, H: int, sampling, quality: int, restart_interval: int) -> bytes:
+    """SOI .. SOS of a W x H image at `quality` (rv_jpeg_write_header, host)."""
+    buf = ctypes.create_string_buffer(640)
+    n = ctypes.c_size_t(0)
+    call("rv_jpeg_write_header", int(W), int(H), jpeg_sampling_code(sampling), int(quality),
+         int(restart_interval), ctypes.addressof(buf), 640, ctypes.addressof(n))
+    return buf.raw[:n.value]
+
+
+def bgr_to_jpeg_coef(frames: torch.Tensor, quality: int = 95, sampling="420",
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(S, H, W, 3) BGR u8 frames on device -> (S, record bytes) quantised DCT
+    coefficient records (the layout jpeg_to_bgr reads), libjpeg's default
+    forward path bit for bit."""
+    x, S, H, W, pitch = _frames(frames)
+    if pitch != 3 * W:
+        x = x.contiguous()
+    samp = jpeg_sampling_code(sampling)
+    n = int(_lib.load().rv_jpeg_record_bytes(W, H, samp))
+    if out is None:
+        out = torch.empty((S, n), dtype=torch.uint8, device=x.device)
+    elif out.shape != (S, n) or not out.is_contiguous() or out.dtype != torch.uint8:
+        raise ValueError(f"out must be a contiguous ({S}, {n}) uint8 tensor")
+    call("rv_jpeg_bgr_to_coef_u8", ptr(x), S, H, W, samp, int(quality), ptr(out), n, stream_ptr())
+    return out
+
+
+def _jpeg_streams(S, W, H, samp, capacity, out, device):
+    stride = jpeg_stream_bound(W, H, samp) if out is None else out.stride(0)
+    if out is None:
+        out = torch.empty((S, stride), dtype=torch.uint8, device=device)
+    elif out.dim() != 2 or out.shape[0] != S or out.stride(1) != 1 or out.dtype != torch.uint8:
+        raise ValueError("out must be (S, stride) uint8 rows")
+    cap = out.shape[1] if capacity is None else int(capacity)
+    return out, stride, cap
+
+
+def jpeg_coef_to_stream(records: torch.Tensor, W: int, H: int, sampling, quality: int,
+                        capacity: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                        ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Device coefficient records of W x H images (from bgr_to_jpeg_coef at
+    `quality`) -> (S, stride) u8 streams: a 16-byte header {magic, image bytes,
+    flags, segments} and the complete JPEG image.  At most `capacity` bytes of
+    each stream are written."""
+    samp = jpeg_sampling_code(sampling)
+    if records.dim() != 2 or records.dtype != torch.uint8 or not records.is_cuda:
+        raise ValueError("expected JPEG coefficient records, uint8 (S, bytes), on the GPU")
+    S = records.shape[0]
+    rstride = records.stride(0) if S > 1 else records.shape[1] // 16 * 16
+    out, stride, cap = _jpeg_streams(S, W, H, samp, capacity, out, records.device)
+    need = int(_lib.load().rv_jpeg_stream_ws_bytes(S, W, H, samp))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=records.device)
+    fh = (1 if samp == 0 else 2) * 8
+    hdr = jpeg_file_header(W, H, samp, quality, (W + fh - 1) // fh)
+    call("rv_jpeg_coef_to_stream", ptr(records), rstride, S, int(W), int(H), samp, hdr, len(hdr),
+         ptr(ws), ws.numel(), ptr(out), stride, cap, stream_ptr())
+    return out
+
+
+def jpeg_encode(frames: torch.Tensor, quality: int = 95, sampling="420",
+                capacity: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(S, H, W, 3) BGR u8 frames on device -> (S, stride) u8 streams
+    (rv_jpeg_encode_bgr_u8; see jpeg_coef_to_stream).  Nothing is read back."""
+    x, S, H, W, pitch = _frames(frames)
+    if pitch != 3 * W:
+        x = x.contiguous()
+    samp = jpeg_sampling_code(sampling)
+    out, stride, cap = _jpeg_streams(S, W, H, samp, capacity, out, x.device)
+    need = int(_lib.load().rv_jpeg_encode_ws_bytes(S, W, H, samp))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    call("rv_jpeg_encode_bgr_u8", ptr(x), S, H, W, samp, int(quality), ptr(ws), ws.numel(),
+         ptr(out), stride, cap, stream_ptr())
+    return out
+
+
 def median(frames: torch.Tensor, k: int = 3, out: Optional[torch.Tensor] = None):
     x, B, H, W, pitch = _frames(frames)
     out = _like(x, out)

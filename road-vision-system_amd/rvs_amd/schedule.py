@@ -225,6 +225,10 @@ class PipelinedRun:
             raise ValueError(f"mode {mode!r}: expected 'native' or 'eager'")
         if sync not in ("stage", "flow"):
             raise ValueError(f"sync {sync!r}: expected 'stage' or 'flow'")
+        if getattr(eng, "recorder", None) is not None:
+            raise RuntimeError("preview.record is enabled: recording runs with step() / "
+                               "step_unit(), beside the schedule, not inside a PipelinedRun "
+                               "(the launch schedule has no encode or file-write op)")
         if eng.detector is None:
             raise ValueError("PipelinedRun needs detect.enabled (a detector-off engine runs "
                              "only the preprocess: use step())")
