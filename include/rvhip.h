@@ -855,6 +855,104 @@ int rv_sink_flush(void* handle);
 /* Write what is queued, flush, close the file, free the ring. */
 int rv_sink_close(void* handle);
 
+/* --- Detection overlays and the compare canvas (csrc/overlay.hip; the
+ * reference's draw_detections, src/vis/draw.py:25-102, and make_canvas,
+ * main_preview.py:12-34).  What the reference computes itself is reproduced
+ * exactly: which detections are drawn and in which order, the colours, the
+ * label strings and every coordinate formula.  Its two OpenCV primitives
+ * (cv2.rectangle, cv2.putText with Hershey strokes) are replaced by the
+ * raster model below, with a fixed bitmap font; pixel parity with cv2's
+ * antialiased text and round-joined thick outlines is not promised.
+ *
+ * Raster model.  Coordinates are integers and ranges inclusive.  Everything
+ * is clipped to the image; colours are BGR u8, written opaque.
+ *   - Painter's order: primitives apply in list order, the last one covering
+ *     a pixel wins.  Per detection: box outline, top label box, top text, then
+ *     bottom label box and bottom text when there are metrics.
+ *   - RV_OVERLAY_FILL (x0,y0)-(x1,y1): every pixel with min(x0,x1) <= x <=
+ *     max(x0,x1), the same in y (cv2's thickness -1).
+ *   - RV_OVERLAY_OUTLINE, thickness t >= 1, a = t / 2, b = (t - 1) / 2: each
+ *     edge line at coordinate c covers c-a .. c+b across and runs from outer
+ *     corner to outer corner (square joins): the filled rectangle
+ *     (x0-a, y0-a)-(x1+b, y1+b) minus the filled rectangle
+ *     (x0+b+1, y0+b+1)-(x1-a-1, y1-a-1).  t = 1 is exactly cv2's pixels.
+ *   - Font: csrc/overlay_font.h, 95 glyphs for ASCII 32..126, each a 6 x 11
+ *     one-bit cell; rows 0..8 above the baseline, rows 9..10 descenders.  A
+ *     byte outside 32..126 is drawn as '?'.
+ *   - RV_OVERLAY_TEXT at origin (x0, y0) = (ox, oy), glyph scale k (1..8):
+ *     byte i occupies x in [ox + 6k*i, ox + 6k*(i+1) - 1], cell row r occupies
+ *     y in [oy - 9k + 1 + k*r, oy - 9k + k*(r+1)] (the last row above the
+ *     baseline ends at y = oy); a set bit paints a k x k block.
+ *   - Text metrics (for cv2.getTextSize): width 6k*len, height 9k, baseline
+ *     2k, whatever the thickness.
+ *   - Text thickness t (1..32; larger values draw as 32): 1 draws the glyphs
+ *     as they are, t >= 2 the union of the glyphs shifted by every dx, dy in
+ *     [-((t-1)/2), t/2] (a square dilation).
+ *   - font_scale -> k on the host: k = max(1, min(8, int(font_scale * 22 / 7
+ *     + 0.5))).
+ *
+ * Display list: a 16-byte header, int32[4] = {count, 0, 0, 0}, followed by
+ * `count` records of RV_OVERLAY_PRIM_BYTES; unused bytes of a record are 0.
+ * Stream s's list of a workspace starts at s * (16 + (5*dmax + 8) * 96). */
+#define RV_OVERLAY_FILL 1
+#define RV_OVERLAY_OUTLINE 2
+#define RV_OVERLAY_TEXT 3
+#define RV_OVERLAY_TEXT_BYTES 64
+#define RV_OVERLAY_PRIM_BYTES 96
+#define RV_OVERLAY_LIST_HEADER_BYTES 16
+#define RV_OVERLAY_CANVAS_PRIMS 8 /* capacity of the canvas list (three label pairs) */
+#define RV_OVERLAY_NAME_BYTES 32  /* a class name: at most 31 bytes and a NUL */
+#define RV_OVERLAY_ANNOTATE 0
+#define RV_OVERLAY_COMPARE_H 1
+#define RV_OVERLAY_COMPARE_V 2
+typedef struct rv_overlay_prim {
+  int32_t kind;          /* RV_OVERLAY_FILL / OUTLINE / TEXT; anything else draws nothing */
+  int32_t x0, y0;        /* a corner; text: the origin (left end of the baseline row) */
+  int32_t x1, y1;        /* the opposite corner; text: 0 */
+  uint8_t b, g, r;       /* colour */
+  uint8_t thickness;     /* outline and text; fill: 0 */
+  uint8_t scale;         /* text: k, 1..8; else 0 */
+  uint8_t len;           /* text: bytes used of `text`, 0..64; else 0 */
+  uint8_t pad[2];
+  uint8_t text[RV_OVERLAY_TEXT_BYTES];
+  int32_t reserved;
+} rv_overlay_prim;
+/* Bytes of S display lists of 5*dmax + 8 records each; 0 for a bad size. */
+size_t rv_overlay_ws_bytes(int S, int dmax);
+/* One step's device results -> S display lists, as draw_detections builds
+ * them (draw.py:34-56 and its two label helpers) on H x W frames: slot i <
+ * det_n[s] of dets (S, dmax, 6: x1 y1 x2 y2 conf cls) is drawn when, after
+ * int() truncation, x2 > x1 and y2 > y1; a skipped detection leaves no gap.
+ * Colour _COLOR_TABLE[cls % 10]; box thickness max(1, thickness), text
+ * thickness one less (at least 1); glyph scale `scale`.  Top label
+ * "ID <track_id> | <name> <conf:.2f>" (no prefix for track_id < 0; <name> is
+ * names[cls] -- nc x 32 bytes, NUL-terminated -- or str(cls) when that is
+ * empty or cls is outside [0, nc)); bottom label "<d:.1f> m / <v:.1f> km/h"
+ * from distance_m / speed_kmh, where NaN means None (left out; both NaN: no
+ * bottom label).  The numbers are formatted as Python's f-strings do,
+ * correctly rounded half to even, for |x| < 1e9; anything larger prints
+ * "---".  One kernel on `stream`, no host reads. */
+int rv_overlay_layout(const float* dets, const int* det_n, const int* track_id,
+                      const double* distance_m, const double* speed_kmh, int S, int dmax, int H,
+                      int W, const uint8_t* names, int nc, int thickness, int scale,
+                      uint8_t* lists, size_t lists_bytes, void* stream);
+/* out[s] = the base image, then stream s's display list, then the canvas list.
+ * RV_OVERLAY_ANNOTATE: the base is proc[s] (S, H, W, 3); `raw` is ignored and
+ * out is (S, H, W, 3).  RV_OVERLAY_COMPARE_H / _V: the base is raw[s], a
+ * divider of divider_px >= 0 pixels of colour (40, 40, 40), then proc[s], side
+ * by side -- out (S, H, 2W + d, 3) -- or stacked -- out (S, 2H + d, W, 3); the
+ * streams' lists are drawn at the PROC pane's offset and clipped to that
+ * pane.  `lists` (device, may be NULL: nothing per stream) holds S lists for
+ * `dmax`; counts are read on the device and capped at the capacity.
+ * `canvas_list` (device, may be NULL) is one list of at most
+ * RV_OVERLAY_CANVAS_PRIMS records in output coordinates, drawn on top of
+ * every stream's image (the RAW / PROC / FPS labels).  proc and raw are only
+ * read; `out` overlapping either is RV_EINVAL.  One kernel on `stream`: one
+ * read and one write of every pixel, no host reads. */
+int rv_overlay_raster(const uint8_t* proc, const uint8_t* raw, int S, int H, int W, int mode,
+                      int divider_px, const uint8_t* lists, int dmax, const uint8_t* canvas_list,
+                      uint8_t* out, void* stream);
+
 /* --- Native launch schedule (csrc/sched.hip; no reference counterpart: the
  * reference runs its chain synchronously, main_preview.py:94-109).  A run of
  * K pipelined steps recorded once as a list of stream-ordered calls of this

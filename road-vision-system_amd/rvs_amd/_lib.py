@@ -111,6 +111,13 @@ _SIGS = {
     "rv_sink_stats": (c_int, [c_void_p, c_void_p]),
     "rv_sink_flush": (c_int, [c_void_p]),
     "rv_sink_close": (c_int, [c_void_p]),
+    # detection overlays and the compare canvas
+    "rv_overlay_ws_bytes": (c_size_t, [c_int, c_int]),
+    "rv_overlay_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                                  c_void_p]),
+    "rv_overlay_raster": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_int, c_void_p, c_void_p, c_void_p]),
     "rv_fog_full_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "rv_fog_full_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -27,6 +27,8 @@ from .handback import Record, handback
 from .io_video.sink import MultiStreamSink, record_settings
 from .preprocess import PreprocessPipeline
 from .track.sort_hip import CameraTable, MultiStreamSort
+from .vis.display_list import canvas_geometry
+from .vis.overlay import OverlayRenderer
 
 
 class RoadVisionEngine:
@@ -134,19 +136,95 @@ class RoadVisionEngine:
         # default chain: CLAHE + median + the detector's LetterBox in one pass
         self.fused_letterbox = self.detector is not None and \
             self.pipeline.letterbox_fusable(self.H, self.W, self.detector.geo)
+        # vis.draw (main_preview.py:113-116): the overlays of annotate() and of
+        # a recording with preview.record.content "annotated" / "compare"
+        draw_cfg = (cfg.get("vis") or {}).get("draw") or {}
+        self.draw_det = bool(draw_cfg.get("det", True)) and self.detector is not None
+        self._draw_args = (int(draw_cfg.get("thickness", 2)), float(draw_cfg.get("font_scale", 0.6)))
+        self._annotators: Dict[bool, OverlayRenderer] = {}
+        self._rec_overlay = None
+        self._rec_n = 0
         if record_cfg is not None:
-            # main_preview.py:130,137 (writer.write): every stream's proc frames
-            # as a Motion-JPEG file, encoded on a side stream of step()
-            self.recorder = MultiStreamSink(record_cfg["paths"], (self.H, self.W),
+            # main_preview.py:130,137 (writer.write): every stream's frames as a
+            # Motion-JPEG file, encoded on a side stream of step()
+            content = record_cfg.get("content", "proc")
+            hw = (self.H, self.W)
+            if content == "compare":
+                cmp_cfg = (cfg.get("preview") or {}).get("compare") or {}
+                hw = canvas_geometry(self.H, self.W, cmp_cfg.get("layout", "h"),
+                                     cmp_cfg.get("divider_px", 4))[:2]
+            self.recorder = MultiStreamSink(record_cfg["paths"], hw,
                                             quality=record_cfg["quality"],
                                             sampling=record_cfg["sampling"], device=self.device)
+            if content != "proc":
+                # display lists rotate as deep as the sink's device buffers
+                self._rec_overlay = self._overlay(content == "compare", self.recorder.nbuf + 1)
+                self._rec_canvas = torch.empty((self.S, hw[0], hw[1], 3), dtype=torch.uint8,
+                                               device=self.device)
 
-    def _record_proc(self, proc: torch.Tensor) -> None:
+    def _overlay(self, compare: bool, slots: int) -> OverlayRenderer:
+        cmp_cfg = (self.cfg.get("preview") or {}).get("compare") or {}
+        return OverlayRenderer(self.S, (self.H, self.W), self.max_det, self.names,
+                               self._draw_args[0], self._draw_args[1], self.device,
+                               compare={k: cmp_cfg[k] for k in ("layout", "divider_px", "label_raw",
+                                                                "label_proc") if k in cmp_cfg}
+                               if compare else None, slots=slots)
+
+    def _record_proc(self, proc: torch.Tensor, frames: Optional[torch.Tensor] = None) -> None:
         """preview.record: queue this step's proc frames for the files.  The
         encode waits (on its own stream) for an event recorded here, behind
-        the preprocess; the current stream goes on with the detector."""
-        if self.recorder is not None:
+        the preprocess; the current stream goes on with the detector.  With
+        overlays to draw the frames are queued by _record_overlay instead,
+        once the step's results exist."""
+        if self.recorder is None:
+            return
+        if self._rec_overlay is None:
             self.recorder.write(proc)
+        elif not self.draw_det:
+            self._record_overlay(proc, frames, None)
+
+    def _record_overlay(self, proc: torch.Tensor, frames: Optional[torch.Tensor], res) -> None:
+        """preview.record.content "annotated" / "compare": the display lists
+        of this step's results `res` (dets, det_n, track_id, distance_m,
+        speed_kmh; None: nothing to draw) are laid out on the current stream
+        -- the next step overwrites the results -- and the raster and the
+        encode run on the sink's stream behind an event recorded here; the
+        current stream waits for neither."""
+        ov = self._rec_overlay
+        if ov.compare is None and res is None:
+            self.recorder.write(proc)  # vis.draw.det false: plain proc
+            return
+        if ov.compare is not None and frames is None:
+            raise ValueError("a compare recording needs the step's raw frames")
+        slot = None
+        if res is not None:
+            slot = self._rec_n % ov.lists.shape[0]
+            self._rec_n += 1
+            ov.layout(*res, slot=slot)
+        raw = frames if ov.compare is not None else None
+        self.recorder.write([proc] if raw is None else [proc, raw],
+                            render=lambda: ov.raster(proc, raw, out=self._rec_canvas, slot=slot))
+
+    def annotate(self, out: Dict[str, torch.Tensor],
+                 frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What the reference shows for one step's `out`: its proc frames
+        with draw_detections (vis.draw.thickness / font_scale) when
+        vis.draw.det is set and the detector runs -- (S, H, W, 3) -- or, given
+        the step's raw `frames`, make_canvas(frames, annotated proc) with
+        preview.compare's layout, divider and labels.  A new device tensor,
+        on the current stream; no FPS text.  Call it before the next step()
+        overwrites the step's results."""
+        compare = frames is not None
+        if compare not in self._annotators:
+            self._annotators[compare] = self._overlay(compare, 1)
+        ov = self._annotators[compare]
+        if self.draw_det and not out.get("no_detector"):
+            ov.layout(out["dets"], out["det_n"], out["track_id"], out["distance_m"],
+                      out["speed_kmh"], slot=0)
+            return ov.raster(out["proc"], frames, slot=0)
+        if not compare:
+            return out["proc"].clone()
+        return ov.raster(out["proc"], frames, slot=None)
 
     def _need_detector(self, what: str) -> None:
         if self.detector is None:
@@ -211,7 +289,7 @@ class RoadVisionEngine:
     def detect_stage(self, frames: torch.Tensor, slot: int = 0) -> torch.Tensor:
         self._need_detector("detect_stage")
         proc, lb = self.preprocess_stage(frames)
-        self._record_proc(proc)
+        self._record_proc(proc, frames)
         self.yolo_stage(lb, slot)
         return proc
 
@@ -241,10 +319,13 @@ class RoadVisionEngine:
             out["seq"] = record.seq
         return out
 
-    def track_pair_stage(self, ts_list, slot: int, records) -> List[Dict[str, torch.Tensor]]:
+    def track_pair_stage(self, ts_list, slot: int, records,
+                         overlay=None) -> List[Dict[str, torch.Tensor]]:
         """Pair mode: NMS of the P*S images of candidate slot `slot` at once,
         then SORT + hand-back of each of the P steps in order (step h owns
-        images [h*S, (h+1)*S))."""
+        images [h*S, (h+1)*S)).  overlay: the (proc, raw frames) of each step
+        of a recording that draws overlays; every step is laid out and queued
+        right behind its SORT, before the next step's overwrites the results."""
         self._need_detector("track_pair_stage")
         S = self.S
         dets, det_n = self.detector.nms(S * len(ts_list), slot)
@@ -253,6 +334,8 @@ class RoadVisionEngine:
             d, n = dets[h * S:(h + 1) * S], det_n[h * S:(h + 1) * S]
             tid, dist, spd = self._metrics(d, n, ts)
             handback(d, n, tid, dist, spd, self.rec_stage, rec.host)
+            if overlay is not None:
+                self._record_overlay(overlay[h][0], overlay[h][1], (d, n, tid, dist, spd))
             outs.append({"record": rec})
         return outs
 
@@ -281,10 +364,12 @@ class RoadVisionEngine:
         self._need_detector("step_unit")
         S = self.S
         procs = [self.preprocess_stage(f, 0, h * S)[0] for h, f in enumerate(frames_list)]
-        for p in procs:
-            self._record_proc(p)
+        for p, f in zip(procs, frames_list):
+            self._record_proc(p, f)
         self.yolo_stage(self.detector.lb[0][:S * len(frames_list)], 0)
-        outs = self.track_pair_stage(ts_list, 0, records)
+        draws = self._rec_overlay is not None and self.draw_det
+        outs = self.track_pair_stage(ts_list, 0, records,
+                                     list(zip(procs, frames_list)) if draws else None)
         for o, p in zip(outs, procs):
             o["proc"] = p
         return outs
@@ -298,11 +383,14 @@ class RoadVisionEngine:
         preprocess runs and every stream's list is empty (main_preview.py:97-99)."""
         if self.detector is None:
             proc, _ = self.preprocess_stage(frames)
-            self._record_proc(proc)
+            self._record_proc(proc, frames)
             return {"proc": proc, "no_detector": True}
         proc = self.detect_stage(frames, 0)
         out = self.track_stage(ts, 0, self.record if record is None else record)
         out["proc"] = proc
+        if self._rec_overlay is not None and self.draw_det:
+            self._record_overlay(proc, frames, (out["dets"], out["det_n"], out["track_id"],
+                                                out["distance_m"], out["speed_kmh"]))
         return out
 
     def results(self, out: Dict[str, torch.Tensor]) -> List[List[Detection]]:

@@ -12,8 +12,11 @@ bytes cross to the host: native writer threads over pinned rings
 (rv_sink_*) copy each image once its encode has finished, without ever making
 the caller's GPU stream wait.
 
-Containers: ``.mjpeg`` / ``.mjpg`` only.  There is no MP4 / AVI muxer, no
-timing in the file, no overlay drawing and no compare canvas.
+Containers: ``.mjpeg`` / ``.mjpg`` only.  There is no MP4 / AVI muxer and no
+timing in the file.  What is recorded is ``preview.record.content``: the bare
+proc frames, the frames with the detection overlays, or the RAW | PROC compare
+canvas; the drawing is ``rvs_amd.vis`` (rv_overlay_raster), which a sink runs
+on its own stream through ``write(..., render=...)``.
 """
 from __future__ import annotations
 
@@ -28,6 +31,8 @@ from .. import _lib
 from .._lib import call, ptr, stream_ptr
 
 _CONTAINERS = (".mjpeg", ".mjpg")
+# preview.record.content: what a recording engine writes
+RECORD_CONTENTS = ("proc", "annotated", "compare")
 
 
 def _device_frames(frames, device) -> torch.Tensor:
@@ -120,20 +125,34 @@ class MultiStreamSink:
                 raise
         self._harr = (ctypes.c_void_p * self.S)(*[h.value for h in self._handles])
 
-    def write(self, batch: torch.Tensor, after: Optional[torch.cuda.Event] = None) -> None:
+    def write(self, batch, after: Optional[torch.cuda.Event] = None, render=None) -> None:
+        """render: a callable that runs on the sink's stream, behind `after`,
+        and returns the (S, H, W, 3) frames to encode -- the overlay raster of
+        a recording engine.  `batch` is then the tensor, or the tensors, it
+        reads (they are kept alive for the sink's stream)."""
         from ..kernels import jpeg_encode
         if not self._handles:
             raise RuntimeError("the sink is closed")
-        if tuple(batch.shape) != (self.S, self.H, self.W, 3) or not batch.is_cuda:
+        inputs = [batch] if isinstance(batch, torch.Tensor) else list(batch)
+        if render is None and (len(inputs) != 1 or not inputs[0].is_cuda or
+                               tuple(inputs[0].shape) != (self.S, self.H, self.W, 3)):
             raise ValueError(f"expected ({self.S}, {self.H}, {self.W}, 3) uint8 frames on the GPU")
         with torch.cuda.device(self.device):
             if after is None:
                 after = torch.cuda.Event()
                 after.record(torch.cuda.current_stream())
             self.stream.wait_event(after)
-            batch.record_stream(self.stream)
+            for t in inputs:
+                t.record_stream(self.stream)
             out = self._bufs[self._n % (self.nbuf + 1)]
             with torch.cuda.stream(self.stream):
+                if render is not None:
+                    batch = render()
+                    if tuple(batch.shape) != (self.S, self.H, self.W, 3):
+                        raise ValueError(f"render() gave {tuple(batch.shape)} frames for a sink "
+                                         f"of ({self.S}, {self.H}, {self.W}, 3)")
+                else:
+                    batch = inputs[0]
                 if self._ws is None:
                     need = int(_lib.load().rv_jpeg_encode_ws_bytes(self.S, self.W, self.H,
                                                                    _code(self.sampling)))
@@ -204,8 +223,10 @@ class VideoSink:
 
 def record_settings(cfg: Optional[dict], n_streams: int) -> Optional[dict]:
     """preview.record of a config -> None when recording is off, else
-    {"paths": one file per stream, "quality", "sampling"}.  Raises for a
-    container other than Motion-JPEG and for several streams sharing a path."""
+    {"paths": one file per stream, "quality", "sampling"}, plus "content" when
+    it is not the default "proc".  Raises for a container other than
+    Motion-JPEG, for several streams sharing a path and for a content other
+    than "proc" / "annotated" / "compare"."""
     rec = ((cfg or {}).get("preview") or {}).get("record") or {}
     if not rec.get("enable", False):
         return None
@@ -221,5 +242,11 @@ def record_settings(cfg: Optional[dict], n_streams: int) -> Optional[dict]:
         raise ValueError(f"preview.record.quality {quality} not in 1..100")
     sampling = str(rec.get("sampling", "420"))
     _code(sampling)
+    content = rec.get("content", "proc")
+    if content not in RECORD_CONTENTS:
+        raise ValueError(f"preview.record.content {content!r}: expected one of {RECORD_CONTENTS}")
     paths = [path.format(stream=s) if "{stream}" in path else path for s in range(n_streams)]
-    return {"paths": paths, "quality": quality, "sampling": sampling}
+    out = {"paths": paths, "quality": quality, "sampling": sampling}
+    if content != "proc":
+        out["content"] = content
+    return out
