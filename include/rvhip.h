@@ -484,7 +484,9 @@ int rv_sort_init(void* state, int S, int tmax, void* stream);
  * min_hits, iou_threshold, speed_window, max_distance (<0 = None), 0}.  H9
  * (nullable = no projector): row-major f64 homography; origin2: projector
  * origin (f32).  Outputs per detection (S x dmax): track id (-1 = None),
- * distance_m and speed_kmh (NaN = None).  tmax <= 8192 and the association
+ * distance_m and speed_kmh (NaN = None); a new track that is dropped in the
+ * same frame (max_staleness < 0, or no free slot) still reports its id and
+ * its box's distance, as the reference does.  tmax <= 8192 and the association
  * workgroup's LDS (about 41 B x tmax + 28 B x dmax + 32 KB) <= 160 KB. */
 int rv_sort_update(void* state_in, void* state_out, int S, int tmax, const float* dets,
                    const int* dcount, int dmax, const double* ts, const double* params6,

@@ -511,11 +511,19 @@ __device__ __forceinline__ void sort_update_row(Track* __restrict__ pool, const 
   out_dist[o] = NAN;
   out_speed[o] = NAN;
   if (j.x == -2) return;  // no detection
-  if (j.x < 0) {          // a new track that did not fit: the id is still consumed
+  const float* de = dets + o * 6;
+  if (j.x < 0) {  // a new track that did not fit or was pruned at once: the id is still consumed
     out_id[o] = j.y;
+    // the reference runs update_metrics on the new track before it drops it
+    // (sort_tracker.py:262-268): its box's distance is reported, the speed is
+    // None (a history of one entry)
+    double X, Y;
+    if (p.has_proj && project(p, 0.5 * ((double)de[0] + (double)de[2]), (double)de[3], X, Y)) {
+      const double dist = distance(p, X, Y);
+      if (!isnone(dist)) out_dist[o] = dist;
+    }
     return;
   }
-  const float* de = dets + o * 6;
   Track& tr = pool[(size_t)s * p.tmax + j.x];
   if (j.y < 0) {  // matched: _Track.update + update_metrics
     if (!kf_done) {  // (else kf_update_rows ran it)
