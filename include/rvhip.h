@@ -256,6 +256,19 @@ int rv_yolo_destroy(void* handle);
  * the sums round differently (within 1 bf16 ulp of the per-tap order).
  * 0: the per-tap k order, bit-identical to the unfused launches. */
 #define RV_YOLO_OPT_C2F_TAP_PAIRS 7
+/* RV_YOLO_OPT_HEAD_SPARSE (default 2): the sparse Detect head.  The decode
+ * runs the class branch alone and lists the candidates (best class score >
+ * conf); the box branch behind model.22.cv2.i.0 -- cv2.i.1, cv2.i.2, DFL,
+ * dist2bbox -- then runs at the candidates only, each from the 3x3
+ * neighbourhood of cv2.i.0's map, instead of densely over every anchor.
+ * Candidate rows, counts and order are bit-identical to the dense head.
+ * 0: dense.  1: sparse wherever the head has the form (a bf16 plan whose
+ * decode would take form 2 of rv_yolo_head_form, and a candidate list is
+ * asked for); other forwards -- raw_out, fp8, wider heads -- stay dense.
+ * 2: auto, sparse as under 1 when the call's conf >= 0.1 and B >= 8.  Other
+ * values: RV_EINVAL.  The sparse kernel is correct at any candidate count,
+ * only slower than the dense convs once most anchors are candidates. */
+#define RV_YOLO_OPT_HEAD_SPARSE 8
 
 /* One bf16 NHWC conv through the detector's conv launcher (layer tests;
  * the building block behind rv_yolo_forward, which the reference's
@@ -340,8 +353,9 @@ int rv_yolo_num_classes(void* handle);
  * one): 0 = unfused last head stage, f32 logits read from HBM; 1 = last stage
  * fused into the decode, class scan over the logits tile in LDS (any plan;
  * always with raw_out); 2 = fused with the class scores kept in registers
- * (YOLOv8n, nc = 80 or nc <= 64, no raw_out).  For tests that must prove
- * which kernel ran. */
+ * (YOLOv8n, nc = 80 or nc <= 64, no raw_out); 3 = form 2 with the class
+ * branch only, followed by the sparse box-branch kernel
+ * (RV_YOLO_OPT_HEAD_SPARSE).  For tests that must prove which kernel ran. */
 int rv_yolo_head_form(void* handle);
 /* scales[n]: one per activation buffer (n = rv_yolo_num_buffers; entries of
  * bf16 / f32 buffers are ignored), each a positive power of two. */

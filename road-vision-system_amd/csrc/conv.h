@@ -41,6 +41,10 @@ struct ConvArgs {
   const float* g2_bias;
   // > 0: this launch record stands for a fused C2f chain (yolo_model.h's
   // Model::fused[fused - 1]); the autotuner leaves it alone
+  // -1: a launch-list placeholder, never launched -- the conv runs per
+  // candidate inside the sparse box-branch kernel (head_box.hip).  It keeps
+  // its launch index so the per-index tuned configurations stay aligned
+  // between dense and sparse forwards of a handle.
   int fused;
   // fp8 (OCP e4m3fn) path: in8 = 1 -> the input (and residual) views hold
   // fp8 codes with per-tensor scales s_in / s_res (value = code * s), the
@@ -178,8 +182,29 @@ struct Cand {  // one detection candidate (Ultralytics NMS row before NMS)
 // logits read from HBM, 1 = fused last stage with the class scan in LDS, 2 =
 // fused with register-resident class scores.
 int decode_segments(const HeadLevel* lv, int nlv);
+// cls_only (the fixed form 2 only; reported as form 3): the class branch
+// alone -- score, class, anchor and the segment counts as above, the box of
+// every candidate row left zero for launch_head_box.
 int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_max, float conf,
                          float* raw, Cand* cand, int cand_cap, int* seg_n, hipStream_t s,
-                         int* form = nullptr);
+                         int* form = nullptr, bool cls_only = false);
+
+// The box branch of one level behind its first conv, evaluated per candidate
+// (head_box.hip): t = cv2.i.0's bf16 output map (64 channels at channel
+// stride t_cs), w1 / b1 = cv2.i.1's packed weights [64][9][64] and bias;
+// cv2.i.2 is the level's HeadLevel::w_box / b_box (cin_b = 64).
+struct HeadBoxLevel {
+  const bf16_t* t;
+  int t_cs;
+  const bf16_t* w1;
+  const float* b1;
+};
+// After a cls_only decode on the same stream: cv2.i.1 at every candidate's
+// anchor (from the 3x3 neighbourhood of t), cv2.i.2, DFL and dist2bbox, the
+// box written into the candidate row in place -- bit for bit the box the
+// dense convs and the full decode give.  Counts and anchors read from
+// seg_n / cand are clamped to their ranges before any address is formed.
+int launch_head_box(const HeadLevel* lv, const HeadBoxLevel* bx, int nlv, int B, int reg_max,
+                    Cand* cand, int cand_cap, const int* seg_n, hipStream_t s);
 
 }  // namespace rv

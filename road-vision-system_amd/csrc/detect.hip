@@ -2,6 +2,7 @@
 // launch_detect_decode of conv.h).
 #include "conv.h"
 #include "conv_common.h"
+#include "head.h"
 
 namespace rv {
 
@@ -9,13 +10,6 @@ namespace rv {
 // Detect head decode: DFL softmax-expectation, dist2bbox (xywh) * stride,
 // class sigmoid; Ultralytics non_max_suppression candidate filter.
 // ---------------------------------------------------------------------------
-struct HeadLevels {
-  HeadLevel lv[4];
-  int start[5];  // first anchor of each level
-  int blk[5];    // first 64-anchor block of each level
-  int nlv;
-};
-
 // One 256-thread workgroup per 64 consecutive anchors of one level: their
 // (64 x cs) f32 head logits are one contiguous span, staged into LDS with
 // coalesced 16-B loads at a padded row stride (cs + 4 floats: rows 20 banks
@@ -38,6 +32,11 @@ struct HeadLevels {
 // Class score: exp + one v_rcp_f32 (no IEEE division sequence).  The raw
 // output and the candidate filter use this same function, so the scores NMS
 // sees are the scores in `raw`.
+//
+// CLASS-ONLY (BOX = false, the fixed head of a sparse forward): the class
+// branch, the candidate filter and the segment counts exactly as above, but no
+// box features, box MFMAs, logits tile or DFL; a candidate row's box stays
+// zero until head_box.hip's kernel, next on the stream, fills it in.
 __device__ __forceinline__ float head_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
@@ -56,17 +55,20 @@ __device__ __forceinline__ float head_sigmoid(float x) {
 // per lane) are loaded by head_weights once per level and stay in VGPRs
 // while the block walks its anchor tiles: per 16-anchor wave tile they were
 // 4.6x the feature bytes, all of it L2 -> CU traffic.
-template <int REG, int KB, int KC, int NCF>
+// BOX = false (the class-only decode): no box weights, features or MFMAs.
+template <int REG, int KB, int KC, int NCF, bool BOX>
 __device__ __forceinline__ void head_weights(const HeadLevel& L, uint4 (&Ab)[KB][REG / 4],
                                              uint4 (&Ac)[KC][NCF]) {
   constexpr int MB = REG / 4;
   const int lane = threadIdx.x & 63, col = lane & 15, quad = lane >> 4;
   constexpr int cinb = KB * 32, cinc = KC * 32;
+  if constexpr (BOX) {
 #pragma unroll
-  for (int k = 0; k < KB; ++k)
+    for (int k = 0; k < KB; ++k)
 #pragma unroll
-    for (int m = 0; m < MB; ++m)
-      Ab[k][m] = *(const uint4*)(L.w_box + (size_t)(m * 16 + col) * cinb + k * 32 + quad * 8);
+      for (int m = 0; m < MB; ++m)
+        Ab[k][m] = *(const uint4*)(L.w_box + (size_t)(m * 16 + col) * cinb + k * 32 + quad * 8);
+  }
 #pragma unroll
   for (int k = 0; k < KC; ++k)
 #pragma unroll
@@ -76,23 +78,25 @@ __device__ __forceinline__ void head_weights(const HeadLevel& L, uint4 (&Ab)[KB]
 
 // one 16-anchor wave tile's feature fragments (B operands): box channels,
 // then class channels of anchor r0 + 16 wave + col
-template <int REG, int KB, int KC>
+template <int REG, int KB, int KC, bool BOX>
 __device__ __forceinline__ void head_feats(const HeadLevel& L, int b, int HW, int r0, int na,
                                            uint4 (&Bb)[KB], uint4 (&Bc)[KC]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, quad = lane >> 4;
   const int an0 = wave * 16 + col;
   const bool ok = an0 < na;
   const bf16_t* fp = L.feat + ((size_t)b * HW + r0 + (ok ? an0 : 0)) * L.feat_cs + quad * 8;
+  if constexpr (BOX) {
 #pragma unroll
-  for (int k = 0; k < KB; ++k)
-    Bb[k] = ok && k * 32 + quad * 8 < L.cin_b ? *(const uint4*)(fp + k * 32) : make_uint4(0, 0, 0, 0);
+    for (int k = 0; k < KB; ++k)
+      Bb[k] = ok && k * 32 + quad * 8 < L.cin_b ? *(const uint4*)(fp + k * 32) : make_uint4(0, 0, 0, 0);
+  }
 #pragma unroll
   for (int k = 0; k < KC; ++k)
     Bc[k] = ok && k * 32 + quad * 8 < L.cin_c ? *(const uint4*)(fp + 4 * REG + k * 32)
                                               : make_uint4(0, 0, 0, 0);
 }
 
-template <int REG, int KB, int KC, int NCF>
+template <int REG, int KB, int KC, int NCF, bool BOX>
 __device__ __forceinline__ void head_mfma_fixed(const HeadLevel& L, const uint4 (&Ab)[KB][REG / 4],
                                                 const uint4 (&Ac)[KC][NCF], const uint4 (&Bb)[KB],
                                                 const uint4 (&Bc)[KC], float* lg, int nc,
@@ -101,7 +105,7 @@ __device__ __forceinline__ void head_mfma_fixed(const HeadLevel& L, const uint4 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63, col = lane & 15, quad = lane >> 4;
   float* row = lg + (size_t)(wave * 16 + col) * (L.cs + 4);
-  {
+  if constexpr (BOX) {
     f32x4 acc[MB];
 #pragma unroll
     for (int m = 0; m < MB; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -163,7 +167,7 @@ __device__ __forceinline__ void head_mfma_fixed(const HeadLevel& L, const uint4 
 }
 
 
-template <int REG, bool FUSED, int KB = 0, int KC = 0, int NCF = 0, int NCT = 0>
+template <int REG, bool FUSED, int KB = 0, int KC = 0, int NCF = 0, int NCT = 0, bool BOX = true>
 __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B, int nc,
                                                             float conf, float* __restrict__ raw,
                                                             Cand* __restrict__ cand, int cap,
@@ -208,15 +212,15 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B,
     const int cs4 = L.cs / 4, ls4 = cs4 + 1;  // row length / LDS row stride in float4
     if constexpr (kFixed) {
       if (l != wl) {
-        head_weights<REG, KB, KC, NCF>(L, Ab, Ac);
+        head_weights<REG, KB, KC, NCF, BOX>(L, Ab, Ac);
         wl = l;
       }
-      if (!pre) head_feats<REG, KB, KC>(L, b, HW, r0, na, Bb, Bc);
-      head_mfma_fixed<REG, KB, KC, NCF>(L, Ab, Ac, Bb, Bc, lg, nc, hbest, hbc);
+      if (!pre) head_feats<REG, KB, KC, BOX>(L, b, HW, r0, na, Bb, Bc);
+      head_mfma_fixed<REG, KB, KC, NCF, BOX>(L, Ab, Ac, Bb, Bc, lg, nc, hbest, hbc);
       // the next tile's features stream in under this tile's decode (same
       // level only; a level change loads them at the top of its iteration)
       pre = t + 1 < tpb && blk + 1 < nblk && r0 + 64 < HW;
-      if (pre) head_feats<REG, KB, KC>(L, b, HW, r0 + 64, min(64, HW - r0 - 64), Bb, Bc);
+      if (pre) head_feats<REG, KB, KC, BOX>(L, b, HW, r0 + 64, min(64, HW - r0 - 64), Bb, Bc);
       __syncthreads();
     } else if constexpr (FUSED) {
       constexpr int MB = REG / 4;  // box fragments (4*REG couts)
@@ -327,37 +331,9 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B,
     const int an = tid >> 2, part = tid & 3;
     const bool live = an < na;
     const float* px = lg + (live ? an : 0) * (L.cs + 4);
-    // DFL side `part`
-    float d;
-    {
-      float v[REG];
-      float mx = -INFINITY;
-      // the side's REG logits are 16-B aligned in the row (cs + 4 floats,
-      // a multiple of 4): ds_read_b128s
-#pragma unroll
-      for (int i = 0; i < REG; i += 4) {
-        const f32x4 q = *(const f32x4*)(px + part * REG + i);
-        v[i] = q[0];
-        v[i + 1] = q[1];
-        v[i + 2] = q[2];
-        v[i + 3] = q[3];
-      }
-#pragma unroll
-      for (int i = 0; i < REG; ++i) mx = fmaxf(mx, v[i]);
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < REG; ++i) {
-        v[i] = __expf(v[i] - mx);
-        sum += v[i];
-      }
-      // softmax probabilities by one reciprocal (v_rcp_f32, <= 1 ulp from
-      // v / sum; the decode tolerance is 2e-3 px)
-      const float rs = __builtin_amdgcn_rcpf(sum);
-      float e = 0.f;
-#pragma unroll
-      for (int i = 0; i < REG; ++i) e += (float)i * (v[i] * rs);
-      d = e;
-    }
+    // DFL side `part` (the class-only form leaves the boxes to head_box.hip)
+    float d = 0.f;
+    if constexpr (BOX) d = dfl_side<REG>(px + part * REG);
     // first maximum of the sigmoid scores.  The fixed head (NCT > 0) found
     // it in registers (head_mfma_fixed: lane (col, quad) of the MFMA layout
     // holds anchor col's result); otherwise lane part scans classes part,
@@ -393,14 +369,11 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B,
     const int r = r0 + (live ? an : 0);
     const int a = lstart + r;
     const int y = r / L.W, x = r - (r / L.W) * L.W;
-    const float ax = (float)x + 0.5f, ay = (float)y + 0.5f;
-    const float x1 = ax - d0, y1 = ay - d1, x2 = ax + d2, y2 = ay + d3;
-    const float cx = (x1 + x2) / 2.0f * L.stride, cy = (y1 + y2) / 2.0f * L.stride;
-    const float w = (x2 - x1) * L.stride, hh = (y2 - y1) * L.stride;
+    const BoxXYWH bx = dist2bbox(d0, d1, d2, d3, x, y, L.stride);
     if (NCT == 0 && raw && live) {  // (the fixed head runs without raw / logits_out)
       for (int c = part; c < nc; c += 4)
         raw[((size_t)b * (4 + nc) + 4 + c) * A + a] = head_sigmoid(pc[c]);
-      const float bxv = part == 0 ? cx : (part == 1 ? cy : (part == 2 ? w : hh));
+      const float bxv = part == 0 ? bx.cx : (part == 1 ? bx.cy : (part == 2 ? bx.w : bx.h));
       raw[((size_t)b * (4 + nc) + part) * A + a] = bxv;
     }
     // Candidates go to this block's own 64-slot segment of the image's list
@@ -420,12 +393,12 @@ __global__ __launch_bounds__(256) void detect_decode_kernel(HeadLevels h, int B,
       const int i = base0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
       if (i < cap) {
-        const float hw = w / 2.0f, hh2 = hh / 2.0f;  // xywh2xyxy
+        const f32x4 xy = BOX ? xywh2xyxy(bx) : f32x4{0.f, 0.f, 0.f, 0.f};
         Cand c;
-        c.x1 = cx - hw;
-        c.y1 = cy - hh2;
-        c.x2 = cx + hw;
-        c.y2 = cy + hh2;
+        c.x1 = xy[0];
+        c.y1 = xy[1];
+        c.x2 = xy[2];
+        c.y2 = xy[3];
         c.score = best;
         c.cls = bc;
         c.anchor = a;
@@ -444,25 +417,10 @@ int decode_segments(const HeadLevel* lv, int nlv) {
 
 int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_max, float conf,
                          float* raw, Cand* cand, int cand_cap, int* cand_n, hipStream_t s,
-                         int* form) {
-  if (nlv < 1 || nlv > 4 || reg_max != 16) {
-    set_error("detect decode: nlv=%d reg_max=%d unsupported", nlv, reg_max);
-    return RV_EINVAL;
-  }
+                         int* form, bool cls_only) {
   HeadLevels h;
-  h.nlv = nlv;
-  h.start[0] = 0;
-  h.blk[0] = 0;
-  int cs = lv[0].cs;
-  for (int i = 0; i < nlv; ++i) {
-    h.lv[i] = lv[i];
-    h.start[i + 1] = h.start[i] + lv[i].H * lv[i].W;
-    h.blk[i + 1] = h.blk[i] + ceil_div(lv[i].H * lv[i].W, 64);
-    if (lv[i].cs != cs || cs % 4 != 0) {
-      set_error("detect decode: head channel strides differ / not a multiple of 4");
-      return RV_EINVAL;
-    }
-  }
+  if (!head_levels(lv, nlv, reg_max, h)) return RV_EINVAL;
+  const int cs = lv[0].cs;
   // the rows hold 4 * reg_max + nc logits (then padding): every class read
   // stays inside the row and the (64 x cs) tile inside 64 KB of LDS
   if (nc < 1 || nc > 128 || cs < 4 * reg_max + nc) {
@@ -480,7 +438,11 @@ int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_ma
   bool fixed = fused && (nc == 80 || nc <= 64) && raw == nullptr;
   for (int i = 0; i < nlv && fixed; ++i)
     fixed = lv[i].cin_b == 64 && lv[i].cin_c == cin_c_fixed && lv[i].logits_out == nullptr;
-  if (form) *form = !fused ? 0 : (fixed ? 2 : 1);
+  if (cls_only && !(fixed && cand)) {
+    set_error("detect decode: the class-only form needs the fixed fused head and a candidate list");
+    return RV_EINVAL;
+  }
+  if (form) *form = !fused ? 0 : (fixed ? (cls_only ? 3 : 2) : 1);
   if (smem > 64 * 1024) {  // only raise the cap when the head needs it (large nc)
     // best effort: a failure surfaces as the launch error reported below
     (void)hipFuncSetAttribute(fused ? (const void*)detect_decode_kernel<16, true>
@@ -505,9 +467,14 @@ int launch_detect_decode(const HeadLevel* lv, int nlv, int B, int nc, int reg_ma
       int tpb = 4;
       while (tpb > 1 && (long)ceil_div(nblk, tpb) * B < 4L * num_cus()) --tpb;
       const dim3 grid(ceil_div(nblk, tpb), B);
-#define RV_FIXED_HEAD(KC_, NCF_)                                                  \
-  detect_decode_kernel<16, true, 2, KC_, NCF_, 16 * NCF_><<<grid, 256, smem, s>>>( \
-      h, B, nc, conf, raw, cand, cand_cap, cand_n, nblk, tpb)
+      // (the class-only form keeps no logits tile)
+#define RV_FIXED_HEAD(KC_, NCF_)                                                           \
+  if (cls_only)                                                                            \
+    detect_decode_kernel<16, true, 2, KC_, NCF_, 16 * NCF_, false><<<grid, 256, 0, s>>>(   \
+        h, B, nc, conf, raw, cand, cand_cap, cand_n, nblk, tpb);                           \
+  else                                                                                     \
+    detect_decode_kernel<16, true, 2, KC_, NCF_, 16 * NCF_><<<grid, 256, smem, s>>>(       \
+        h, B, nc, conf, raw, cand, cand_cap, cand_n, nblk, tpb)
       switch (nc == 80 ? 5 : ceil_div(nc, 16)) {
         case 5: RV_FIXED_HEAD(3, 5); break;
         case 4: RV_FIXED_HEAD(2, 4); break;

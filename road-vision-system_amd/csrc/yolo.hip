@@ -68,6 +68,12 @@ static void plan(Model& M) {
 
 static const View NO_VIEW{-1, 0, 0};
 
+// RV_YOLO_OPT_HEAD_SPARSE = 2 (auto): the sparse head runs when the call's
+// conf is at least kSparseAutoConf and its batch at least kSparseAutoBatch
+// ("Sparse box branch", has the measured curves behind both).
+constexpr float kSparseAutoConf = 0.1f;
+constexpr int kSparseAutoBatch = 8;
+
 // What one conv reads and writes: input view at map level li -> up to two
 // output views (up: a nearest-2x upsampled copy), an optional residual, and
 // for a 1x1 conv an optional virtual concat input that stands in for `in`.
@@ -252,6 +258,22 @@ struct Exec {
     const ConvArgs a = args(*c, io);
     trace(*c, io);
     launch(a, *c, flops_of(*c, io.li), launch_bytes(a));
+  }
+
+  // Conv `name` of a sparse-head forward: not launched (it runs per candidate
+  // inside the sparse box-branch kernel).  Its trace record stays, with no
+  // output view (out0.buf = -1: the map is never written), and so does its
+  // launch index: a placeholder (ConvArgs::fused = -1) in the launch list with
+  // no profile slot, so the per-index tuned configurations line up between
+  // dense and sparse forwards of one handle.
+  void conv_in_sparse(const std::string& name, const ConvIO& io) {
+    if (status) return;
+    const ConvSpec* c = spec(name);
+    if (!c) return;
+    ConvArgs a = args(*c, io);
+    a.fused = -1;
+    trace(*c, {io.in, io.li, NO_VIEW});
+    M->launches.push_back(a);
   }
 
   // Two convs that share their input buffer, kernel size, stride and
@@ -535,13 +557,32 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
   const bool fork =
       M->head_streams && B >= 8 && M->side[0] && M->side[1] && !M->prof.active();
   const hipStream_t main_s = E.s;
+  // Sparse head: the box branch behind cv2.i.0 runs at the candidates only
+  // (head_box.hip) after a class-only decode.  Only where the decode takes
+  // its fixed form (bf16 plan, 64-wide box branch, 80 or <= 64 classes, no
+  // raw output / logits copy) and a candidate list is asked for; auto picks
+  // it for pipeline-sized batches at a conf where candidates are sparse.
+  const bool fixed_head = fuse_head && !E.f8 && !raw_out && cand && v.c2d == 64 &&
+                          (v.nc == 80 || v.nc <= 64) && v.c3p == (v.nc == 80 ? 80 : 64);
+  const bool sparse =
+      fixed_head && (M->head_sparse == 1 ||
+                     (M->head_sparse == 2 && conf >= kSparseAutoConf && B >= kSparseAutoBatch));
   HeadLevel hl[3] = {};
+  HeadBoxLevel hbx[3] = {};
   auto head_level = [&](int i) {
     const std::string a = "model.22.cv2." + std::to_string(i), c = "model.22.cv3." + std::to_string(i);
     const View da{M->DA[i], dcs, 0}, fb{M->DB[i], dcs, 0}, fc{M->DB[i], dcs, v.c2d},
         lg{M->HD[i], hcs, 0};
     E.conv_pair(a + ".0", P[i], c + ".0", P[i], 3 + i, da);
-    E.conv_pair(a + ".1", da, c + ".1", View{M->DA[i], dcs, v.c2d}, 3 + i, fb);
+    if (sparse) {
+      const ConvSpec* p1 = E.spec(a + ".1");
+      if (!p1) return E.status;
+      E.conv_in_sparse(a + ".1", {da, 3 + i, fb});
+      E.conv(c + ".1", {View{M->DA[i], dcs, v.c2d}, 3 + i, fc});
+      hbx[i] = HeadBoxLevel{(const bf16_t*)E.ptr(M->DA[i]), dcs, E.wptr(*p1), E.bptr(*p1)};
+    } else {
+      E.conv_pair(a + ".1", da, c + ".1", View{M->DA[i], dcs, v.c2d}, 3 + i, fb);
+    }
     HeadLevel& L = hl[i];
     L.logits = (const float*)E.ptr(M->HD[i]);
     L.H = M->map_h[3 + i];
@@ -593,8 +634,10 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
       E.status = hip_check(hipStreamWaitEvent(main_s, M->ev_join[i], 0), "head join wait");
   if (E.status) return E.status;
   if (M->prof.active()) M->prof.n_fwd++;
-  return launch_detect_decode(hl, 3, B, v.nc, v.reg, conf, raw_out, (Cand*)cand, cand_cap, cand_n,
-                              E.s, &M->head_form);
+  const int st = launch_detect_decode(hl, 3, B, v.nc, v.reg, conf, raw_out, (Cand*)cand, cand_cap,
+                                      cand_n, E.s, &M->head_form, sparse);
+  if (st || !sparse) return st;
+  return launch_head_box(hl, hbx, 3, B, v.reg, (Cand*)cand, cand_cap, cand_n, E.s);
 }
 
 // Part 4 must continue the handle's last part 3, part 2 its last part 0 / 1 / 4:
@@ -714,6 +757,10 @@ extern "C" int rv_yolo_set_option(void* h, int opt, int value) {
       return RV_OK;
     case RV_YOLO_OPT_C2F_TAP_PAIRS:
       M->c2f_tap_pairs = value != 0;
+      return RV_OK;
+    case RV_YOLO_OPT_HEAD_SPARSE:
+      RV_CHECK_ARG(value >= 0 && value <= 2, "head sparse option %d not in {0, 1, 2}", value);
+      M->head_sparse = value;
       return RV_OK;
     default:
       set_error("unknown yolo option %d", opt);

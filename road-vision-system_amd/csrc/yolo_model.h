@@ -138,9 +138,11 @@ struct Model {
   int head_streams = 1;            // RV_YOLO_OPT_HEAD_STREAMS
   int fuse_cv1 = 1;                // RV_YOLO_OPT_FUSE_CV1
   int c2f_tap_pairs = 1;           // RV_YOLO_OPT_C2F_TAP_PAIRS
+  int head_sparse = 2;             // RV_YOLO_OPT_HEAD_SPARSE: 0 dense, 1 sparse, 2 auto
   // decode form of the last forward that reached the decode (rv_yolo_head_form;
   // -1 before one): 0 unfused last stage, 1 fused + LDS class scan, 2 fused
-  // with register-resident class scores
+  // with register-resident class scores, 3 the class-only form 2 followed by
+  // the sparse box-branch kernel
   int head_form = -1;
   std::vector<Buf> bufs;
   int nA = 0;

@@ -76,7 +76,9 @@ extern "C" int rv_yolo_autotune(void* h, const uint8_t* lb, int B, void* ws, siz
   std::vector<ConvCfg> cands(512);
   for (size_t i = 0; i < L.size() && !st; ++i) {
     const ConvArgs& a = L[i];
-    if (a.fused > 0) continue;  // fused C2f chains have one kernel configuration
+    // fused C2f chains have one kernel configuration (and a sparse-head
+    // placeholder none: the autotuner's own forward is dense)
+    if (a.fused != 0) continue;
     if (verify)
       for (int d = 0; d < 2; ++d)
         if (out_bytes(a, d))
@@ -178,7 +180,7 @@ extern "C" int rv_yolo_conv_candidates(void* h, int idx, int* cfg6, int cap) {
   RV_CHECK_ARG(idx >= 0 && idx < (int)M->launches.size(),
                "launch %d not in the last forward (%d launches)", idx, (int)M->launches.size());
   const ConvArgs& a = M->launches[idx];
-  if (a.fused > 0) return 0;
+  if (a.fused != 0) return 0;
   std::vector<ConvCfg> c(512);
   const int n = std::min(conv_candidates(a, c.data(), (int)c.size()), (int)c.size());
   for (int i = 0; i < n && i < cap && cfg6; ++i) to6(c[i], cfg6 + 6 * i);

@@ -30,6 +30,7 @@ CAND_BYTES = 32
 # rv_yolo_set_option numbers (include/rvhip.h RV_YOLO_OPT_*)
 OPT_RAW_UNFUSED, OPT_FUSE_C2F, OPT_STEM_X1, OPT_HEAD_STREAMS, OPT_FUSE_CV1 = 1, 2, 3, 4, 5
 OPT_C2F_TAP_PAIRS = 7
+OPT_HEAD_SPARSE = 8
 
 
 def scale_boxes_params(img1_hw, img0_hw):
@@ -252,11 +253,19 @@ class YoloEngine:
         False / 0 = none."""
         self._set_option(OPT_FUSE_C2F, 1 if on is True else (0 if on is False else int(on)))
 
+    def set_head_sparse(self, mode) -> None:
+        """The Detect box branch behind cv2.i.0 at the candidates only
+        (RV_YOLO_OPT_HEAD_SPARSE; bit-identical candidates): False / 0 =
+        dense, True / 1 = sparse wherever the head has the form, 2 or "auto"
+        (default) = sparse for batches of 8 and more at conf >= 0.1."""
+        self._set_option(OPT_HEAD_SPARSE, 2 if mode == "auto" else int(mode))
+
     def head_form(self, lane: int = 0) -> int:
         """Decode form of forward context `lane`'s last forward
         (rv_yolo_head_form): 0 unfused last head stage, 1 fused with the LDS
-        class scan, 2 fused with register-resident class scores; -1 before
-        any forward."""
+        class scan, 2 fused with register-resident class scores, 3 the
+        class-only form 2 + the sparse box-branch kernel; -1 before any
+        forward."""
         return int(_lib.load().rv_yolo_head_form(self._hs[lane]))
 
     def letterbox(self, frames: torch.Tensor, slot: int = 0, off: int = 0) -> torch.Tensor:
