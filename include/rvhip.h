@@ -458,7 +458,15 @@ size_t rv_nms_smem_bytes(void);
  * segments of 64 rows, cap <= 65536 rows per image).  Every candidate is
  * sorted (score desc, anchor asc); only the first max_nms of them enter the
  * greedy pass (Ultralytics non_max_suppression's max_nms = 30000: top
- * max_nms by score).  scale5 = {gain (f32 of the python gain), pad_x, pad_y,
+ * max_nms by score).  seg_n[b * nseg + j] rows of segment j are used, from
+ * its first slot on; a count outside [0, 64] is clamped to that range, and
+ * rows past the count are never read.  Ties in score resolve by the rows'
+ * anchor field (< 65536, distinct within an image), not by the slot.
+ * iou: the largest f32 not above the reference's double threshold -- the
+ * kernel suppresses on (double)ovr > (double)iou with an f32 ovr, which then
+ * equals torchvision's `ovr > iou_threshold` for every double threshold
+ * (the nearest f32 of 0.6 or 0.3 lies above the double and would keep a pair
+ * whose IoU is exactly that f32).  scale5 = {gain (f32 of the python gain), pad_x, pad_y,
  * clip_w, clip_h}; keep_mask4 (nullable = keep all): 128-bit class mask
  * (classes_keep); out: B x max_det x 6 {x1,y1,x2,y2,conf,cls} in score
  * order, out_n[B]; cand_total (nullable): candidates per image before

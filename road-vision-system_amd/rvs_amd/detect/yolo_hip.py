@@ -42,6 +42,19 @@ def scale_boxes_params(img1_hw, img0_hw):
     return gain, pad_x, pad_y
 
 
+def iou_threshold_f32(iou: float) -> float:
+    """rv_nms_postprocess's f32 threshold for the configured (double)
+    iou_thres.  torchvision's nms tests `ovr > iou_threshold` with the f32
+    IoU promoted to double; for an f32 ovr that holds exactly when ovr > r, r
+    the largest f32 not above the double.  Rounding to nearest gives a larger
+    r for thresholds like 0.6 and 0.3 (f32(0.6) = 0.60000002...), and a pair
+    whose IoU is that f32 would be kept where the reference suppresses it."""
+    r = np.float32(iou)
+    if float(r) > float(iou):
+        r = np.nextafter(r, np.float32(-np.inf))
+    return float(r)
+
+
 def class_mask(classes_keep: Sequence[int]) -> Optional[np.ndarray]:
     keep = set(int(x) for x in classes_keep)
     if not keep:
@@ -92,6 +105,7 @@ class YoloEngine:
         self.max_batch = int(max_batch)
         self.conf, self.iou, self.max_det, self.max_wh = float(conf), float(iou), int(max_det), \
             float(max_wh)
+        self._iou_arg = (self.iou, iou_threshold_f32(self.iou))
         self.max_nms = int(max_nms)  # Ultralytics non_max_suppression default
         self.geo = kernels.letterbox_geometry(self.H, self.W, imgsz, stride)
         self.in_h, self.in_w = self.geo[0], self.geo[1]
@@ -340,8 +354,10 @@ class YoloEngine:
     def nms(self, B: int, slot: int = 0):
         """NMS + scale_boxes + class filter of candidate slot `slot`, into
         that slot's outputs."""
+        if self._iou_arg[0] != self.iou:  # (double threshold, its f32 argument)
+            self._iou_arg = (self.iou, iou_threshold_f32(self.iou))
         call("rv_nms_postprocess", ptr(self.cand[slot]), ptr(self.seg_n[slot]), B, self.cap,
-             self._nseg_cur, self.iou, self.max_det, self.max_nms, self.max_wh, ptr(self.scale5),
+             self._nseg_cur, self._iou_arg[1], self.max_det, self.max_nms, self.max_wh, ptr(self.scale5),
              ptr(self.keep),
              ptr(self.dets_s[slot]), ptr(self.det_n_s[slot]), ptr(self.cand_n_s[slot]),
              ptr(self.nms_ws_s[slot]), self.nms_ws_s[slot].numel(), stream_ptr())
