@@ -205,9 +205,21 @@ int rv_letterbox_u8(const uint8_t* in, uint8_t* out, int B, int H, int W,
                     int pitch, const int* geo, void* stream);
 
 
-/* --- YOLOv8 model (the Ultralytics graph run by model.predict,
+/* --- YOLOv8 / YOLOv5u model (the Ultralytics graph run by model.predict,
  * yolo_ultralytics.py:16-35).  variant: 0=n 1=s 2=m 3=l 4=x (yolov8.yaml
- * scales).  Weights are BN-fused conv weights + biases in Ultralytics
+ * scales: Conv / C2f / SPPF / Detect at model.22); 5=n 6=s 7=m 8=l 9=x of
+ * YOLOv5u (yolov5.yaml scales: Conv k6 / C3 / SPPF under the same Detect at
+ * model.24 -- the anchor-free "u" checkpoints yolov5n.pt ... resolve to).
+ * Every entry that takes a variant accepts 0..9; YOLOv5u plans are bf16 only
+ * (RV_YOLO_DTYPE_FP8 with a variant >= 5: RV_EINVAL), class counts 1..128 as
+ * for YOLOv8.  YOLOv5u's model.0 is a 6x6 stride-2 pad-2 conv on the u8
+ * letterbox (in_h, in_w multiples of 32, so its map is in_h/2 x in_w/2): it
+ * runs on i8 MFMAs with exact integer sums under the contract of the 3x3
+ * first conv -- f64 weights w[o][2-ch][ky][kx] / 255 as integers at 2^-23 of
+ * the channel's largest magnitude, three balanced base-256 digits, the value
+ * s (65536 T0 + (256 T1 + T2)) + b in f32 -- within 1 bf16 ulp of the f64
+ * conv; out-of-image taps are the conv's zero padding.
+ * Weights are BN-fused conv weights + biases in Ultralytics
  * state_dict order (rv_yolo_conv_info), flattened as, per conv,
  * weight[cout][cin][k][k] then bias[cout] (f32). */
 int rv_yolo_num_convs(int variant);
@@ -269,6 +281,11 @@ int rv_yolo_destroy(void* handle);
  * values: RV_EINVAL.  The sparse kernel is correct at any candidate count,
  * only slower than the dense convs once most anchors are candidates. */
 #define RV_YOLO_OPT_HEAD_SPARSE 8
+/* RV_YOLO_OPT_STEM6_FUSED: YOLOv5nu (C0 = 16, c2 = 32) runs model.0 (k6) and
+ * model.1 as one kernel with the P1 map in LDS; X1 is bit-identical to the
+ * two launches'.  Raw parity forwards with RV_YOLO_OPT_RAW_UNFUSED run the
+ * two launches.  0: always two launches.  No effect on other plans. */
+#define RV_YOLO_OPT_STEM6_FUSED 9
 
 /* One bf16 NHWC conv through the detector's conv launcher (layer tests;
  * the building block behind rv_yolo_forward, which the reference's

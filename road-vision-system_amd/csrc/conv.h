@@ -107,15 +107,26 @@ int launch_conv0(const uint8_t* img, int B, int H, int W, const Conv0Q& q, int C
 int launch_conv0_fp8(const uint8_t* img, int B, int H, int W, const Conv0Q& q, int C0,
                      uint8_t* out, int out_cs, float s_out, hipStream_t s);
 
+// YOLOv5u's first conv (3 -> C0 in {16, 32, 48, 64, 80}, k6 s2 p2) with the
+// same arithmetic contract; H and W multiples of 32 (the X0 map is H/2 x W/2).
+// q.d holds three 64-deep K blocks per digit and channel, [3][C0][3][64]: row
+// pair p = ky / 2, K slot 32 (ky & 1) + 3 kx + ch over the window row's 18 BGR
+// bytes, every other slot zero (yolo_def.hip pack_conv0q6); q.s / q.b / q.c as
+// above, q.c summed over all 108 taps.
+int launch_conv0_k6(const uint8_t* img, int B, int H, int W, const Conv0Q& q, int C0, bf16_t* out,
+                    int out_cs, hipStream_t s);
+
 // conv0 and model.1 (C0 = 16 -> C1 = 32, k3 s2) fused: the P1 map never
 // leaves LDS.  w1/b1: model.1's packed weights / bias; out (nullable): X1
 // (NHWC, channel stride out_cs).  w2/b2/out2 (nullable): the following 1x1
 // conv 32 -> 32 (model.2.cv1) run from the registers into out2 (channel
-// stride out2_cs), bit-identical to the unfused 1x1 kernels.
+// stride out2_cs), bit-identical to the unfused 1x1 kernels.  k6: YOLOv5nu's
+// stem -- q0 in launch_conv0_k6's form, conv0-k6 + model.1 with X1
+// bit-identical to the unfused pair's; no w2 / out2.
 int launch_stem(const uint8_t* img, int B, int H, int W, const Conv0Q& q0, int C0,
                 const bf16_t* w1, const float* b1, int C1, bf16_t* out, int out_cs,
                 hipStream_t s, const bf16_t* w2 = nullptr, const float* b2 = nullptr,
-                bf16_t* out2 = nullptr, int out2_cs = 0);
+                bf16_t* out2 = nullptr, int out2_cs = 0, bool k6 = false);
 
 // SPPF pooling: buf holds x in channels [0, c); writes maxpool5, maxpool5^2
 // and maxpool5^3 (= clipped 5/9/13 windows) into [c,2c), [2c,3c), [3c,4c).

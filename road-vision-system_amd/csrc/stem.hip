@@ -1,6 +1,7 @@
 // YOLOv8 stem kernels for gfx950: conv0 (model.0, 3 -> 16, k3 s2 from the u8
 // letterbox on i8 MFMAs) alone, and the fused stem (conv0 + model.1 +
-// model.2.cv1) with the P1 map kept in LDS.
+// model.2.cv1) with the P1 map kept in LDS; and YOLOv5u's model.0 (3 -> C0,
+// k6 s2 p2, conv0-k6 below).
 //
 // Reference: the first layers of the YOLOv8 graph Ultralytics runs inside
 // model.predict (src/detect/yolo_ultralytics.py:28-35; Conv = conv + fused
@@ -8,6 +9,7 @@
 // -amdgpu-mfma-vgpr-form=1 (Makefile), so the i8 / bf16 MFMA accumulators
 // live in VGPRs -- conv0's epilogue reads its three digit sums per output
 // without v_accvgpr_read (they are the stem's VALU hot spot).
+#include <type_traits>
 #include "conv_common.h"
 
 namespace rv {
@@ -184,6 +186,187 @@ int launch_conv0_fp8(const uint8_t* img, int B, int H, int W, const Conv0Q& q, i
 }
 
 // ---------------------------------------------------------------------------
+// conv0-k6: YOLOv5u's model.0, 3 -> C0, k6 s2 p2, from letterboxed u8 BGR,
+// SiLU, bf16 out.  H and W are multiples of 32, so the X0 map is H/2 x W/2.
+// ---------------------------------------------------------------------------
+// The arithmetic contract is conv0's (above): integer weights at 2^-23 of the
+// channel's largest magnitude in three balanced base-256 i8 digits
+// (yolo_def.hip pack_conv0q6), x - 128 fed to v_mfma_i32_16x16x64_i8 with the
+// accumulator started at 128 sum D_i, 256 T1 + T2 exact in i32, one fma, then
+// scale, bias and SiLU in f32.  With 108 taps |T_i| <= 108 * 128 * 255 < 2^24.
+//
+// K layout: 3 x 64, one window-row pair per MFMA (not 2 x 64 with a byte
+// shuffle).  Window row ky of X0 pixel (Y, X) is the 18 contiguous bytes from
+// byte 6X - 6 of letterbox row 2Y - 2 + ky.  In the MFMA of pair p, lane quads
+// 0, 1 supply bytes 0..15 / 16..31 of row 2p and quads 2, 3 those of row
+// 2p + 1 (K slot 32 (ky & 1) + 3 kx + ch; slots 18..31 carry zero weights).
+// Why: a lane's 16-byte operand is then 16 consecutive bytes of ONE letterbox
+// row, so it is built as conv0 builds its own -- dword buffer loads from the
+// aligned base, v_alignbyte_b32 (6X - 6 is even: shift 0 or 2) and an XOR
+// 0x80 -- with no per-byte v_perm, and every padding decision is per dword:
+// row bytes 3W are a multiple of 4, so each dword lies wholly inside or
+// wholly outside the image row.  The 2 x 64 form would save 3 of the 9 MFMAs
+// per 16 x 16 fragment, but its 6-byte row remainders straddle lanes and
+// need a v_perm network; the kernel is bound by its window loads and the
+// SiLU epilogue, not by the MFMA pipe (9 x 16 cycles per 256 outputs).
+// Out-of-image dwords (rows < 0 or >= H, the two padding pixels left of
+// X = 0, which in a flat buffer alias the end of the previous row, and the
+// two right of X = W/2 - 1, which alias the next row) are loaded from voffset
+// kOOB: the buffer range check returns zero, the conv's zero padding.  Lanes
+// of quads 1 and 3 need bytes 16, 17 only: one dword, the other four loads
+// are sent out of range (zero weights there in any case).
+// ---------------------------------------------------------------------------
+struct C6Win {
+  uint32_t w[3][5];
+  int sh;
+};
+
+__device__ __forceinline__ C6Win conv6_window(__amdgpu_buffer_rsrc_t r, int Y, int X, int quad, int H,
+                                              int rowb, bool valid) {
+  C6Win win;
+  const int h = quad & 1;
+  const int start = 6 * X - 6;
+  win.sh = start & 3;  // 0 or 2 (two's complement: X = 0 gives base -8, shift 2)
+  const int cb = start - win.sh + 16 * h;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    const int row = 2 * Y - 2 + 2 * p + (quad >> 1);
+    const bool ok = valid && (unsigned)row < (unsigned)H;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+      const int c = cb + 4 * i;
+      const bool in = ok && (unsigned)c < (unsigned)rowb && (h == 0 || i == 0);
+      const uint32_t vo = in ? (uint32_t)(row * rowb + c) : kOOB;
+      win.w[p][i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)vo, 0, 0);
+    }
+  }
+  return win;
+}
+
+__device__ __forceinline__ i32x4 conv6_bop(const C6Win& w, int p) {
+  i32x4 b;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    b[j] = (int)(__builtin_amdgcn_alignbyte(w.w[p][j + 1], w.w[p][j], w.sh) ^ 0x80808080u);
+  return b;
+}
+
+// digits of cout rows c0 + 16 m + col (A operands, one per digit and row
+// pair) and the lane's 4 output channels' accumulator starts, scale and bias
+template <int MR>
+struct C6Wts {
+  i32x4 d[MR][3][3], c[MR][3];
+  f32x4 s[MR], b[MR];
+  __device__ __forceinline__ void load(const Conv0Q& q, int C0, int c0, int col, int quad) {
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+          d[m][t][p] = *(const i32x4*)(q.d + (((size_t)t * C0 + c0 + 16 * m + col) * 3 + p) * 64 + 16 * quad);
+        c[m][t] = *(const i32x4*)(q.c + (size_t)t * C0 + c0 + 16 * m + 4 * quad);
+      }
+      s[m] = *(const f32x4*)(q.s + c0 + 16 * m + 4 * quad);
+      b[m] = *(const f32x4*)(q.b + c0 + 16 * m + 4 * quad);
+    }
+  }
+};
+
+// one 16-pixel fragment: lane (col, quad) -> SiLU(conv0-k6) of output
+// channels c0 + 16 m + 4 quad .. +3 of the fragment's pixel col
+template <int MR>
+__device__ __forceinline__ void conv6_frag(const C6Wts<MR>& W, const C6Win& win, f32x4 (&v)[MR]) {
+  i32x4 X[3];
+#pragma unroll
+  for (int p = 0; p < 3; ++p) X[p] = conv6_bop(win, p);
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    i32x4 t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      t[i] = W.c[m][i];
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        t[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(W.d[m][i][p], X[p], t[i], 0, 0, 0);
+    }
+    float w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float u = fmaf((float)t[0][i], 65536.0f, (float)(t[1][i] * 256 + t[2][i]));
+      w[i] = fmaf(W.s[m][i], u, W.b[m][i]);
+    }
+    silu4(w);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[m][i] = w[i];
+  }
+}
+
+// Unfused conv0-k6: conv0_kernel's tiling (a workgroup is 4 x 64 output
+// pixels, wave w owns row w, 4 fragments of 16 pixels, fragment j + 1's
+// window loads in flight while fragment j runs); blockIdx.y selects a group
+// of MR 16-channel fragments (the 27 digit operands per fragment stay in
+// registers: MR <= 3).
+template <int MR>
+__global__ __launch_bounds__(256) void conv0k6_kernel(const uint8_t* __restrict__ img, int B, int H,
+                                                      int W, Conv0Q q, int C0,
+                                                      uint16_t* __restrict__ out, int out_cs) {
+  const int Ho = H / 2, Wo = W / 2;
+  const int tiles_x = (Wo + kC0TW - 1) / kC0TW;
+  const int tiles_y = (Ho + kC0TH - 1) / kC0TH;
+  int bid = blockIdx.x;
+  const int tx = bid % tiles_x;
+  bid /= tiles_x;
+  const int ty = bid % tiles_y;
+  const int b = bid / tiles_y;
+  const int c0 = 16 * MR * blockIdx.y;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63, col = lane & 15, quad = lane >> 4;
+  const int oy = ty * kC0TH + wave;
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(img + (size_t)b * H * W * 3), 0, H * W * 3, kRsrcFlags);
+  C6Wts<MR> Wt;
+  Wt.load(q, C0, c0, col, quad);
+  C6Win nxt = conv6_window(r, oy, tx * kC0TW + col, quad, H, W * 3, oy < Ho && tx * kC0TW + col < Wo);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ox = tx * kC0TW + 16 * j + col;
+    const C6Win cur = nxt;
+    if (j < 3) nxt = conv6_window(r, oy, ox + 16, quad, H, W * 3, oy < Ho && ox + 16 < Wo);
+    f32x4 v[MR];
+    conv6_frag<MR>(Wt, cur, v);
+    if (oy >= Ho || ox >= Wo) continue;
+    const size_t opix = (((size_t)b * Ho + oy) * Wo + ox) * out_cs;
+#pragma unroll
+    for (int m = 0; m < MR; ++m)
+      *(uint2*)(out + opix + c0 + 16 * m + 4 * quad) =
+          make_uint2(pack_bf16x2(v[m][0], v[m][1]), pack_bf16x2(v[m][2], v[m][3]));
+  }
+}
+
+int launch_conv0_k6(const uint8_t* img, int B, int H, int W, const Conv0Q& q, int C0, bf16_t* out,
+                    int out_cs, hipStream_t s) {
+  if (H <= 0 || W <= 0 || H % 32 || W % 32 || out_cs < C0 || out_cs % 4) {
+    set_error("conv0-k6: input %dx%d must be positive multiples of 32, out_cs %d >= C0 %d", H, W,
+              out_cs, C0);
+    return RV_EINVAL;
+  }
+  const int blocks = B * ceil_div(H / 2, kC0TH) * ceil_div(W / 2, kC0TW);
+  uint16_t* o = (uint16_t*)out;
+  switch (C0) {
+    case 16: conv0k6_kernel<1><<<dim3(blocks, 1), 256, 0, s>>>(img, B, H, W, q, C0, o, out_cs); break;
+    case 32: conv0k6_kernel<2><<<dim3(blocks, 1), 256, 0, s>>>(img, B, H, W, q, C0, o, out_cs); break;
+    case 48: conv0k6_kernel<3><<<dim3(blocks, 1), 256, 0, s>>>(img, B, H, W, q, C0, o, out_cs); break;
+    case 64: conv0k6_kernel<2><<<dim3(blocks, 2), 256, 0, s>>>(img, B, H, W, q, C0, o, out_cs); break;
+    case 80: conv0k6_kernel<1><<<dim3(blocks, 5), 256, 0, s>>>(img, B, H, W, q, C0, o, out_cs); break;
+    default:
+      set_error("conv0-k6 C0=%d unsupported", C0);
+      return RV_EINVAL;
+  }
+  return launch_status("conv0_k6");
+}
+
+// ---------------------------------------------------------------------------
 // Fused stem: conv0 (3 -> C0 = 16, k3 s2, from the u8 letterbox), model.1
 // (16 -> 32, k3 s2) and model.2.cv1 (32 -> 32 1x1) in one kernel.  The P1
 // map (X0, the network's largest activation) only ever lives in LDS: each
@@ -216,6 +399,13 @@ int launch_conv0_fp8(const uint8_t* img, int B, int H, int W, const Conv0Q& q, i
 // with the operands (and k order) of the unfused 1x1 kernels --
 // bit-identical -- and X1 never reaches HBM (out == nullptr; out !=
 // nullptr still writes it, for parity tests).
+//
+// K6 (YOLOv5nu): conv0 is conv0-k6 (the same X0 tile, conv6_window /
+// conv6_frag per fragment) and model.1 runs one half-zero 32-deep k-step per
+// tap in (ky, kx) order -- the operands and the accumulation order of the
+// patch kernel on a 16-channel input -- so X1 is bit-identical to the unfused
+// pair's (the tap pairs of the k3 stem agree to 1 bf16 ulp only).  No 1x1 is
+// fused behind it (C3's cv1 / cv2 are 32 -> 16).
 constexpr int kStR = 8, kStC = 32;           // X1 tile
 constexpr int kStXR = 2 * kStR + 1;          // X0 tile rows (17)
 constexpr int kStXE = kStC + 1;              // even X0 tile columns (33)
@@ -227,6 +417,7 @@ constexpr int kStNpx = kStXR * kStXW;        // 1105 X0 pixels per tile: 70 conv
 static_assert(kStXE == 33 && kStXW - kStXE == 32 && kStXR % 2 == 1,
               "conv0 strips: 2 x 16 even + 2 x 16 odd columns, 9 row pairs");
 
+template <bool K6>
 __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ img, int B, int H,
                                                    int W, Conv0Q q0,
                                                    const uint16_t* __restrict__ w1,
@@ -264,8 +455,12 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
   //      pixel's 16-B half (see the swizzle): fragment a's in quads 0 and 2,
   //      b's in quads 1 and 3.
   {
-    C0Wts<1> Wt;
-    Wt.load(q0, 16, col, quad);
+    using Win = typename std::conditional<K6, C6Win, C0Win>::type;
+    typename std::conditional<K6, C6Wts<1>, C0Wts<1>>::type Wt;
+    if constexpr (K6)
+      Wt.load(q0, 16, 0, col, quad);
+    else
+      Wt.load(q0, 16, col, quad);
     const int rowb = W * 3;
     const int jl = (wave < 2 ? 16 * wave : kStXE + 16 * (wave - 2)) + col;  // stored column
     const int X = xx0 + (wave < 2 ? 2 * jl : 2 * (jl - kStXE) + 1);
@@ -278,7 +473,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
     // inline constant (-16), unlike kOOB, which costs a v_bfrev per select
     constexpr uint32_t kOOBi = 0xFFFFFFF0u;
     // the window of strip pixel (Y, X), Y wave-uniform (conv0_window's bytes)
-    auto strip_win = [&](int Y) {
+    auto strip_win3 = [&](int Y) {
       C0Win w;
       w.sh = sh;
       const bool ok = lq && (unsigned)Y < (unsigned)H0 && (unsigned)(2 * Y - 1 + quad) < (unsigned)H;
@@ -287,6 +482,24 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
       w.w1 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)(vb + 4u), 0, 0);
       w.w2 = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(r, (int)(vb + 8u), 0, 0);
       return w;
+    };
+    auto strip_win = [&](int Y) -> Win {
+      if constexpr (K6)
+        return conv6_window(r, Y, X, quad, H, rowb, xin && (unsigned)Y < (unsigned)H0);
+      else
+        return strip_win3(Y);
+    };
+    auto edge_win = [&](int Y, int X_, bool valid) -> Win {
+      if constexpr (K6)
+        return conv6_window(r, Y, X_, quad, H, rowb, valid);
+      else
+        return conv0_window(r, Y, X_, quad, H, rowb, valid);
+    };
+    auto frag = [&](const Win& w, f32x4 (&v)[1]) {
+      if constexpr (K6)
+        conv6_frag<1>(Wt, w, v);
+      else
+        conv0_frag<1>(Wt, conv0_bop(w), v);
     };
     // pair 8's b fragment: wave 0 rows 0-15, wave 1 row 16 (lane 0)
     const int ye = wave == 0 ? col : kStXR - 1;
@@ -297,10 +510,10 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
     // bit 2 of a stored slot is bit 2 of its column (72 = 0 mod 8)
     const int sbase = ((quad & 1) * kStXS + jl) * 32 + (((quad >> 1) ^ ((jl >> 2) & 1)) << 4);
     const int se = (ye * kStXS + kStXE - 1) * 32 + ((quad >> 1) << 4);
-    C0Win na = strip_win(xy0), nb = strip_win(xy0 + 1);
+    Win na = strip_win(xy0), nb = strip_win(xy0 + 1);
 #pragma unroll
     for (int i = 0; i < (kStXR + 1) / 2; ++i) {
-      const C0Win ca = na, cb = nb;
+      const Win ca = na, cb = nb;
       const bool last = 2 * i + 1 == kStXR;
       const int Ya = xy0 + 2 * i;
       const bool cka = xin && (unsigned)Ya < (unsigned)H0;
@@ -310,11 +523,11 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
         nb = strip_win(Ya + 3);
       } else if (2 * i + 3 == kStXR) {
         na = strip_win(Ya + 2);
-        nb = conv0_window(r, Ye, Xe, quad, H, rowb, ine);
+        nb = edge_win(Ye, Xe, ine);
       }
       f32x4 va[1], vb[1];
-      conv0_frag<1>(Wt, conv0_bop(ca), va);
-      conv0_frag<1>(Wt, conv0_bop(cb), vb);
+      frag(ca, va);
+      frag(cb, vb);
       // outside the X0 map the value is model.1's zero padding
       uint32_t a0 = cka ? pack_bf16x2(va[0][0], va[0][1]) : 0u;
       uint32_t a1 = cka ? pack_bf16x2(va[0][2], va[0][3]) : 0u;
@@ -337,11 +550,21 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
   // model.1 A fragments (all 6 k-steps, L2-resident weights) while the
   // conv0 stores drain
   constexpr int MR = 2, NR = 4;
-  bf16x8 A[3][2][MR];
+  constexpr int NP = K6 ? 3 : 2;  // k-steps per window row: taps (K6) or tap pairs
+  bf16x8 A[3][NP][MR];
 #pragma unroll
   for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
+    for (int p = 0; p < NP; ++p) {
+      if constexpr (K6) {  // tap (ky, p): 16 channels + 16 zero weights, natural k order
+#pragma unroll
+        for (int m = 0; m < MR; ++m) {
+          const int co = 8 * (col >> 2) + 4 * m + (col & 3);
+          A[ky][p][m] = __builtin_bit_cast(
+              bf16x8, *(const uint4*)(w1 + ((size_t)co * 9 + ky * 3 + p) * 32 + quad * 8));
+        }
+        continue;
+      }
       const int kx = 2 * p + (quad >> 1);  // quads 0,1: tap 2p; quads 2,3: tap 2p+1
 #pragma unroll
       for (int m = 0; m < MR; ++m) {
@@ -360,7 +583,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
 #pragma unroll
     for (int n = 0; n < NR; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
   // this lane's B column: X1 pixel (row 2 wave + n / 2, col (n & 1) 16 + col)
-  int bb0[NR], bb1[NR];
+  int bb0[NR], bb1[NR], bb2[NR];
   // byte address of half h of stored pixel s (the swizzle above)
   auto xaddr = [](int s_, int h) { return s_ * 32 + ((h ^ ((s_ >> 2) & 1)) << 4); };
 #pragma unroll
@@ -371,15 +594,23 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
     bb0[n] = quad < 2 ? xaddr(rs + c, quad) : xaddr(rs + kStXE + c, quad - 2);
     // pair 1: tap kx 2 (even c + 1); quads 2,3 (phantom tap) read the same
     bb1[n] = xaddr(rs + c + 1, quad & 1);
+    if constexpr (K6) {
+      // one tap per k-step: kx 0 even c, kx 1 odd c, kx 2 even c + 1; quads
+      // 2, 3 (zero weights) read the same halves as quads 0, 1
+      bb0[n] = xaddr(rs + c, quad & 1);
+      bb1[n] = xaddr(rs + kStXE + c, quad & 1);
+      bb2[n] = xaddr(rs + c + 1, quad & 1);
+    }
   }
 #pragma unroll
   for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
+    for (int p = 0; p < NP; ++p) {
       bf16x8 Bf[NR];
 #pragma unroll
       for (int n = 0; n < NR; ++n)
-        Bf[n] = __builtin_bit_cast(bf16x8, *(const uint4*)(xs + (p ? bb1[n] : bb0[n]) + ky * kStRowB));
+        Bf[n] = __builtin_bit_cast(
+            bf16x8, *(const uint4*)(xs + (p == 0 ? bb0[n] : (p == 1 ? bb1[n] : bb2[n])) + ky * kStRowB));
 #pragma unroll
       for (int m = 0; m < MR; ++m)
 #pragma unroll
@@ -454,16 +685,23 @@ __global__ __launch_bounds__(256) void stem_kernel(const uint8_t* __restrict__ i
 
 int launch_stem(const uint8_t* img, int B, int H, int W, const Conv0Q& q0, int C0,
                 const bf16_t* w1, const float* b1, int C1, bf16_t* out, int out_cs,
-                hipStream_t s, const bf16_t* w2, const float* b2, bf16_t* out2, int out2_cs) {
-  if (C0 != 16 || C1 != 32 || (!out && !out2) || (out2 && (!w2 || !b2))) {
+                hipStream_t s, const bf16_t* w2, const float* b2, bf16_t* out2, int out2_cs,
+                bool k6) {
+  if (C0 != 16 || C1 != 32 || (!out && !out2) || (out2 && (!w2 || !b2)) ||
+      (k6 && (out2 || H % 32 || W % 32))) {
     set_error("stem: C0=%d C1=%d (fused stem needs 16 -> 32) / outputs", C0, C1);
     return RV_EINVAL;
   }
   const int H0 = (H + 1) / 2, W0 = (W + 1) / 2;
   const int H1 = (H0 + 1) / 2, W1 = (W0 + 1) / 2;
   const int blocks = B * ceil_div(H1, kStR) * ceil_div(W1, kStC);
-  stem_kernel<<<blocks, 256, 0, s>>>(img, B, H, W, q0, (const uint16_t*)w1, b1, (uint16_t*)out,
-                                     out_cs, (const uint16_t*)w2, b2, (uint16_t*)out2, out2_cs);
+  if (k6)
+    stem_kernel<true><<<blocks, 256, 0, s>>>(img, B, H, W, q0, (const uint16_t*)w1, b1, (uint16_t*)out,
+                                             out_cs, nullptr, nullptr, nullptr, 0);
+  else
+    stem_kernel<false><<<blocks, 256, 0, s>>>(img, B, H, W, q0, (const uint16_t*)w1, b1,
+                                              (uint16_t*)out, out_cs, (const uint16_t*)w2, b2,
+                                              (uint16_t*)out2, out2_cs);
   return launch_status("stem");
 }
 

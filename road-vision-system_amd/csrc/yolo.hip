@@ -1,4 +1,4 @@
-// YOLOv8 model plan + forward (the detector backend behind
+// YOLOv8 / YOLOv5u model plan + forward (the detector backend behind
 // src/detect/yolo_ultralytics.py:7-53; the model definition and the weight
 // packer are in yolo_def.hip).
 //
@@ -12,12 +12,77 @@
 
 namespace rv {
 
+// The Detect head's buffers (both families) and the anchor count
+static void plan_heads(Model& M) {
+  const Variant& v = M.def.v;
+  for (int i = 0; i < 3; ++i) {
+    const std::string l = std::to_string(i);
+    // class branch c3p wide, logits rows hcs floats: the padding channels
+    // (none in the 80-class plans) hold exact zeros
+    M.DA[i] = M.newbuf("DA" + l, 3 + i, v.c2d + v.c3p);
+    M.DB[i] = M.newbuf("DB" + l, 3 + i, v.c2d + v.c3p, false, true);  // bf16: the decode's features
+    M.HD[i] = M.newbuf("HD" + l, 3 + i, v.hcs, true);
+  }
+  M.nA = M.map_h[3] * M.map_w[3] + M.map_h[4] * M.map_w[4] + M.map_h[5] * M.map_w[5];
+}
+
+// YOLOv5u (yolov5.yaml): one buffer per activation.  A C3 block's concat
+// buffer holds [last bottleneck's output | cv2's output] (2c wide, cv3's
+// input); t_i = "prefix.t.i" is the input of bottleneck i (t_0 = cv1's
+// output) and "prefix.m.i" the output of its 1x1 conv.  CAT17 / CAT20 are the
+// yaml's concats 19 = [model.18 | model.14] and 22 = [model.21 | model.10];
+// concats 12 and 16 (behind the two Upsamples) are never materialised.
+static void plan_v5u(Model& M) {
+  const Variant& v = M.def.v;
+  M.CAT14 = M.CAT11 = -1;
+  M.X0 = M.newbuf("X0", 1, v.c1);
+  M.X1 = M.newbuf("X1", 2, v.c2);
+  M.C2 = M.newbuf("C2", 2, v.c2);
+  M.X2 = M.newbuf("X2", 2, v.c2);
+  M.X3 = M.newbuf("X3", 3, v.c3);
+  M.C4 = M.newbuf("C4", 3, v.c3);
+  M.X4 = M.newbuf("X4", 3, v.c3);
+  M.X5 = M.newbuf("X5", 4, v.c4);
+  M.C6 = M.newbuf("C6", 4, v.c4);
+  M.X6 = M.newbuf("X6", 4, v.c4);
+  M.X7 = M.newbuf("X7", 5, v.c5);
+  M.C8 = M.newbuf("C8", 5, v.c5);
+  M.X8 = M.newbuf("X8", 5, v.c5);
+  M.SP = M.newbuf("SP", 5, 4 * (v.c5 / 2));
+  M.X9 = M.newbuf("X9", 5, v.c5);
+  M.CAT20 = M.newbuf("CAT20", 5, 2 * v.c4);
+  M.C12 = M.newbuf("C12", 4, v.c4);
+  M.X13 = M.newbuf("X13", 4, v.c4);
+  M.CAT17 = M.newbuf("CAT17", 4, 2 * v.c3);
+  M.C15 = M.newbuf("C15", 3, v.c3);
+  M.X15 = M.newbuf("X15", 3, v.c3);
+  M.C18 = M.newbuf("C18", 4, v.c4);
+  M.X18 = M.newbuf("X18", 4, v.c4);
+  M.C21 = M.newbuf("C21", 5, v.c5);
+  M.X21 = M.newbuf("X21", 5, v.c5);
+  plan_heads(M);
+  struct C3Def {
+    const char* p;
+    int level, c2, n;
+  };
+  const C3Def cs[] = {{"model.2", 2, v.c2, v.nb},  {"model.4", 3, v.c3, v.nm},
+                      {"model.6", 4, v.c4, v.nx},  {"model.8", 5, v.c5, v.nb},
+                      {"model.13", 4, v.c4, v.nb}, {"model.17", 3, v.c3, v.nb},
+                      {"model.20", 4, v.c4, v.nb}, {"model.23", 5, v.c5, v.nb}};
+  for (const C3Def& c : cs)
+    for (int i = 0; i < c.n; ++i) {
+      M.newbuf(std::string(c.p) + ".t." + std::to_string(i), c.level, c.c2 / 2);
+      M.newbuf(std::string(c.p) + ".m." + std::to_string(i), c.level, c.c2 / 2);
+    }
+}
+
 static void plan(Model& M) {
   const Variant& v = M.def.v;
   for (int i = 0; i < 6; ++i) {
     M.map_h[i] = M.H >> i;
     M.map_w[i] = M.W >> i;
   }
+  if (v.family == kFamilyV5u) return plan_v5u(M);
   M.X0 = M.newbuf("X0", 1, v.c1);
   M.X1 = M.newbuf("X1", 2, v.c2);
   M.C2 = M.newbuf("C2", 2, (2 + v.nb) * (v.c2 / 2));
@@ -41,14 +106,7 @@ static void plan(Model& M) {
   M.X18 = M.newbuf("X18", 4, v.h18);
   M.C21 = M.newbuf("C21", 5, (2 + v.nb) * (v.h21 / 2));
   M.X21 = M.newbuf("X21", 5, v.h21);
-  for (int i = 0; i < 3; ++i) {
-    const std::string l = std::to_string(i);
-    // class branch c3p wide, logits rows hcs floats: the padding channels
-    // (none in the 80-class plans) hold exact zeros
-    M.DA[i] = M.newbuf("DA" + l, 3 + i, v.c2d + v.c3p);
-    M.DB[i] = M.newbuf("DB" + l, 3 + i, v.c2d + v.c3p, false, true);  // bf16: the decode's features
-    M.HD[i] = M.newbuf("HD" + l, 3 + i, v.hcs, true);
-  }
+  plan_heads(M);
   // one temp per bottleneck (its first conv's output), named "prefix.m.i":
   // no buffer is ever overwritten inside a forward, so every layer stays
   // inspectable
@@ -63,7 +121,6 @@ static void plan(Model& M) {
   for (const C2fDef& c : cs)
     for (int i = 0; i < c.n; ++i)
       M.newbuf(std::string(c.p) + ".m." + std::to_string(i), c.level, c.c2 / 2);
-  M.nA = M.map_h[3] * M.map_w[3] + M.map_h[4] * M.map_w[4] + M.map_h[5] * M.map_w[5];
 }
 
 static const View NO_VIEW{-1, 0, 0};
@@ -116,6 +173,7 @@ struct Exec {
     fuse_c2f = fusing && M->fuse_c2f;
     fuse_c2f32 = fuse_c2f && M->fuse_c2f == 2;
     cat14 = v.h12 + v.c3, cat11 = v.c5 + v.c4, cat20 = v.h18 + v.c5, cat17 = v.h15 + v.h12;
+    if (v.family == kFamilyV5u) cat14 = cat17 = 2 * v.c3, cat11 = cat20 = 2 * v.c4;
   }
 
   void* ptr(int buf) const { return ws + off[buf]; }
@@ -418,7 +476,95 @@ struct Exec {
     }
     conv(p + ".cv2", {View{cb, cs, 0}, li, io.o0, io.up0, io.o1, io.up1});
   }
+
+  // C3(prefix), YOLOv5u: the block's input (io.in / io.vin at map io.li) ->
+  // cv1 -> n bottlenecks (1x1 then 3x3, t + ... with shortcut), the last one
+  // writing channels [0, c) of the concat buffer cb; cv2 on the same input
+  // -> [c, 2c); cv3 on cb -> the block's outputs.  One launch per conv.
+  void c3(const std::string& p, const ConvIO& io, int cb, int c2, int n, bool shortcut) {
+    const int c = c2 / 2, li = io.li;
+    auto tbuf = [&](int i) { return View{M->buf_of(p + ".t." + std::to_string(i)), c, 0}; };
+    conv(p + ".cv1", {io.in, li, tbuf(0), 0, NO_VIEW, 0, NO_VIEW, io.vin});
+    for (int i = 0; i < n; ++i) {
+      const std::string q = p + ".m." + std::to_string(i);
+      const View tin = tbuf(i), tmp{M->buf_of(q), c, 0};
+      const View tout = i + 1 < n ? tbuf(i + 1) : View{cb, 2 * c, 0};
+      conv(q + ".cv1", {tin, li, tmp});
+      conv(q + ".cv2", {tmp, li, tout, 0, NO_VIEW, 0, shortcut ? tin : NO_VIEW});
+    }
+    conv(p + ".cv2", {io.in, li, View{cb, 2 * c, c}, 0, NO_VIEW, 0, NO_VIEW, io.vin});
+    conv(p + ".cv3", {View{cb, 2 * c, 0}, li, io.o0, io.up0, io.o1, io.up1});
+  }
 };
+
+// YOLOv5u, segment A: model.0 (k6 s2 p2 from the u8 letterbox, its own
+// kernel: Exec::out_dim's pad = k / 2 does not hold for it), model.1, model.2
+static int seg_stem_v5u(Exec& E, const uint8_t* lb) {
+  Model* M = E.M;
+  const Variant& v = M->def.v;
+  const View x0{M->X0, v.c1, 0}, x1{M->X1, v.c2, 0}, x2{M->X2, v.c2, 0};
+  const ConvSpec& c0 = M->def.convs[0];
+  const uint8_t* qb = M->dev + M->def.q_off;
+  const float* qs = (const float*)(qb + 9 * (size_t)c0.cout * 64);
+  const Conv0Q q0{(const int8_t*)qb, qs, qs + c0.cout, (const int32_t*)(qs + 2 * c0.cout)};
+  const double px0 = (double)E.B * M->map_h[1] * M->map_w[1];
+  const double px1 = (double)E.B * M->map_h[2] * M->map_w[2];
+  const double f0 = 2.0 * px0 * c0.cout * 108, by_in = (double)E.B * M->H * M->W * 3 + M->def.q_bytes;
+  // both forms are timed like the YOLOv8 fused stem: profile slot
+  // per_fwd - 1, which no conv launch index reaches
+  const int slot = M->prof.per_fwd - 1;
+  // conv0-k6 + model.1 fused (YOLOv5nu; the P1 map stays in LDS) unless the
+  // caller asked for the raw prediction with RV_YOLO_OPT_RAW_UNFUSED set
+  const int i1 = M->def.find("model.1");
+  if (E.fusing && M->stem6_fused && c0.cout == 16 && v.c2 == 32 && i1 >= 0) {
+    const ConvSpec& c1 = M->def.convs[i1];
+    E.trace(c1, {x0, 1, x1});
+    E.status = M->prof.timed(slot, E.s, 0, f0 + 2.0 * px1 * c1.cout * c1.cin * 9,
+                             by_in + px1 * 2.0 * c1.cout + 2.0 * c1.cout * 9 * 32, [&] {
+                               return launch_stem(lb, E.B, M->H, M->W, q0, c0.cout, E.wptr(c1),
+                                                  E.bptr(c1), c1.cout, (bf16_t*)E.ptr(M->X1), v.c2,
+                                                  E.s, nullptr, nullptr, nullptr, 0, true);
+                             });
+  } else {
+    E.status = M->prof.timed(slot, E.s, 0, f0, by_in + px0 * 2.0 * c0.cout, [&] {
+      return launch_conv0_k6(lb, E.B, M->H, M->W, q0, c0.cout, (bf16_t*)E.ptr(M->X0), v.c1, E.s);
+    });
+    E.conv("model.1", {x0, 1, x1});
+  }
+  E.c3("model.2", {x1, 2, x2}, M->C2, v.c2, v.nb, true);
+  return E.status;
+}
+
+// YOLOv5u, segment B: model.3 .. model.17 (the rest of the backbone, SPPF and
+// the top-down neck).  The yaml's Upsample + Concat pairs (11-12, 15-16) are
+// virtual concat inputs of the two 1x1 convs that read each of them.
+static int seg_backbone_v5u(Exec& E) {
+  Model* M = E.M;
+  const Variant& v = M->def.v;
+  const int sc = v.c5 / 2;
+  const View x2{M->X2, v.c2, 0}, x3{M->X3, v.c3, 0}, p3{M->X4, v.c3, 0}, x5{M->X5, v.c4, 0},
+      p4{M->X6, v.c4, 0}, x7{M->X7, v.c5, 0}, x8{M->X8, v.c5, 0}, sp{M->SP, 4 * sc, 0},
+      x9{M->X9, v.c5, 0}, x13{M->X13, v.c4, 0};
+  // model.10 / model.14 as the bottom-up concats 22 / 19 hold them
+  const View t10{M->CAT20, E.cat20, v.c4}, t14{M->CAT17, E.cat17, v.c3};
+  const VIn vin13{t10, 1, p4, v.c4}, vin17{t14, 1, p3, v.c3};
+  E.conv("model.3", {x2, 2, x3});
+  E.c3("model.4", {x3, 3, p3}, M->C4, v.c3, v.nm, true);
+  E.conv("model.5", {p3, 3, x5});
+  E.c3("model.6", {x5, 4, p4}, M->C6, v.c4, v.nx, true);
+  E.conv("model.7", {p4, 4, x7});
+  E.c3("model.8", {x7, 5, x8}, M->C8, v.c5, v.nb, true);
+  E.conv("model.9.cv1", {x8, 5, sp});
+  if (!E.status)
+    E.status = launch_sppf_pool((bf16_t*)E.ptr(M->SP), E.B, M->map_h[5], M->map_w[5], sc, E.s);
+  E.conv("model.9.cv2", {sp, 5, x9});
+  E.conv("model.10", {x9, 5, t10});
+  E.c3("model.13", {t10, 4, x13, 0, NO_VIEW, 0, NO_VIEW, &vin13}, M->C12, v.c4, v.nb, false);
+  E.conv("model.14", {x13, 4, t14});
+  E.c3("model.17", {t14, 3, View{M->X15, v.h15, 0}, 0, NO_VIEW, 0, NO_VIEW, &vin17}, M->C15, v.c3,
+       v.nb, false);
+  return E.status;
+}
 
 // A forward is three consecutive segments over one Exec, each returning
 // E.status.  Segment A: the stem (model.0, model.1) and model.2
@@ -570,7 +716,8 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
   HeadLevel hl[3] = {};
   HeadBoxLevel hbx[3] = {};
   auto head_level = [&](int i) {
-    const std::string a = "model.22.cv2." + std::to_string(i), c = "model.22.cv3." + std::to_string(i);
+    const std::string a = M->def.head + "cv2." + std::to_string(i),
+                      c = M->def.head + "cv3." + std::to_string(i);
     const View da{M->DA[i], dcs, 0}, fb{M->DB[i], dcs, 0}, fc{M->DB[i], dcs, v.c2d},
         lg{M->HD[i], hcs, 0};
     E.conv_pair(a + ".0", P[i], c + ".0", P[i], 3 + i, da);
@@ -622,12 +769,22 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
     if (!r && e) E.status = e;
     return r ? r : e;
   };
+  // the bottom-up neck: a stride-2 conv into the level's concat, then its
+  // block (YOLOv8: model.16, C2f 18, model.19, C2f 21; YOLOv5u: model.18,
+  // C3 20, model.21, C3 23)
+  const bool v5 = v.family == kFamilyV5u;
   if (E.status || forked_head(0)) return E.status;
-  E.conv("model.16", {P[0], 3, c17});
-  E.c2f("model.18", {c17, 4, P[1]}, M->C18, v.h18, v.nb, false);
+  E.conv(v5 ? "model.18" : "model.16", {P[0], 3, c17});
+  if (v5)
+    E.c3("model.20", {c17, 4, P[1]}, M->C18, v.h18, v.nb, false);
+  else
+    E.c2f("model.18", {c17, 4, P[1]}, M->C18, v.h18, v.nb, false);
   if (E.status || forked_head(1)) return E.status;
-  E.conv("model.19", {P[1], 4, c20});
-  E.c2f("model.21", {c20, 5, P[2]}, M->C21, v.h21, v.nb, false);
+  E.conv(v5 ? "model.21" : "model.19", {P[1], 4, c20});
+  if (v5)
+    E.c3("model.23", {c20, 5, P[2]}, M->C21, v.h21, v.nb, false);
+  else
+    E.c2f("model.21", {c20, 5, P[2]}, M->C21, v.h21, v.nb, false);
   if (E.status || head_level(2)) return E.status;
   if (fork)
     for (int i = 0; i < 2 && !E.status; ++i)
@@ -758,6 +915,9 @@ extern "C" int rv_yolo_set_option(void* h, int opt, int value) {
     case RV_YOLO_OPT_C2F_TAP_PAIRS:
       M->c2f_tap_pairs = value != 0;
       return RV_OK;
+    case RV_YOLO_OPT_STEM6_FUSED:
+      M->stem6_fused = value != 0;
+      return RV_OK;
     case RV_YOLO_OPT_HEAD_SPARSE:
       RV_CHECK_ARG(value >= 0 && value <= 2, "head sparse option %d not in {0, 1, 2}", value);
       M->head_sparse = value;
@@ -798,6 +958,7 @@ extern "C" int rv_yolo_forward(void* h, const uint8_t* lb, int B, void* ws, size
 }
 
 // part 0: the whole forward (segments A-C).  part 1: A-B, stem .. model.15
+// (YOLOv5u: .. model.17; its segments end at the same places of the graph)
 // (the backbone and the top-down neck: the bandwidth-heavy P2/P3 layers).
 // part 2: C, the rest (the bottom-up neck, the Detect heads and the decode:
 // small latency-bound launches), reading part 1's activations from the same
@@ -826,7 +987,8 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
   static const int SEGS[5] = {7, 3, 4, 1, 2};  // per part: bit 0 = segment A, 1 = B, 2 = C
   const int segs = SEGS[part];
   auto here = [&] { return Resume{M->li_base + (int)M->launches.size(), B, ws}; };
-  if ((segs & 1) && seg_stem(E, lb)) return E.status;
+  const bool v5 = M->def.v.family == kFamilyV5u;
+  if ((segs & 1) && (v5 ? seg_stem_v5u(E, lb) : seg_stem(E, lb))) return E.status;
   if (part == 3) {
     M->after_stem = here();
     // part 3 rewrote the start of the workspace: a part 2 now needs the part 4
@@ -834,7 +996,7 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
     M->after_neck = Resume{};
   }
   if (segs & 2) {
-    if (seg_backbone(E)) return E.status;
+    if (v5 ? seg_backbone_v5u(E) : seg_backbone(E)) return E.status;
     M->after_neck = here();
   }
   return (segs & 4) ? seg_heads(E, raw_out, conf, cand, cand_cap, cand_n) : RV_OK;

@@ -1,6 +1,6 @@
-// YOLOv8 model definition (yolo_def.hip): the canonical conv list of a
-// variant (Ultralytics state_dict order, BN already fused into conv weight +
-// bias) and the layout of its packed weight blob.  Host code only.
+// YOLOv8 / YOLOv5u model definition (yolo_def.hip): the canonical conv list
+// of a variant (Ultralytics state_dict order, BN already fused into conv
+// weight + bias) and the layout of its packed weight blob.  Host code only.
 #pragma once
 #include <string>
 #include <vector>
@@ -25,11 +25,21 @@ struct Variant {
   int c1, c2, c3, c4, c5;   // backbone widths (P1..P5)
   int h12, h15, h18, h21;   // head widths
   int nb, nm;               // C2f repeats for "3" and "6"
+  int nx = 0;               // YOLOv5u: C3 repeats for "9" (model.6)
+  int family = 0;           // kFamilyV8 (C2f graph, yolov8.yaml) / kFamilyV5u (C3 graph, yolov5.yaml)
   int c2d, c3d;             // Detect branch widths (the Ultralytics ones)
   int nc = 80, reg = 16;
   int c3p;                  // c3d as the plan runs it: padded to a multiple of 8
   int hcs;                  // f32 logits row stride: 4 * reg + nc padded to a multiple of 4
 };
+
+// Variants 0..4: YOLOv8 n, s, m, l, x; 5..9: YOLOv5u n, s, m, l, x (the
+// anchor-free re-release of YOLOv5: yolov5.yaml's C3 graph under the YOLOv8
+// Detect head).  For YOLOv5u h15 / h18 / h21 are the Detect inputs' widths
+// (model.17 / 20 / 23: c3, c4, c5) and h12 is model.14's (c3).
+constexpr int kFamilyV8 = 0, kFamilyV5u = 1;
+constexpr int kNumVariants = 10;
+inline int family_of(int variant) { return variant >= 5 ? kFamilyV5u : kFamilyV8; }
 
 // class counts a plan supports: the NMS class mask is 4 x 32 bits wide
 constexpr int kMinClasses = 1, kMaxClasses = 128;
@@ -39,9 +49,15 @@ struct ModelDef {
   int dtype = 0;  // RV_YOLO_DTYPE_BF16 / RV_YOLO_DTYPE_FP8
   std::vector<ConvSpec> convs;
   // conv 0's integer form (the i8 MFMA conv0, conv.h Conv0Q), after every
-  // conv's block: digits [3][C0][64] i8, scales [C0] f32, biases [C0] f32,
-  // accumulator starts [3][C0] i32
+  // conv's block.  YOLOv8 (k3): digits [3][C0][64] i8, scales [C0] f32,
+  // biases [C0] f32, accumulator starts [3][C0] i32.  YOLOv5u (k6 s2 p2,
+  // Conv0Q with three 64-deep K blocks per digit): digits [3][C0][3][64] i8
+  // -- digit t, channel o, row pair p = ky / 2, K slot 32 (ky & 1) + 3 kx + ch
+  // over the window row's 18 BGR bytes, slots 18..31 and 50..63 zero --, then
+  // scales [C0] f32, biases [C0] f32, accumulator starts [3][C0] i32
+  // (128 x the digit's sum over all 108 taps).
   size_t q_off = 0, q_bytes = 0;
+  std::string head = "model.22.";  // the Detect module's state_dict prefix
   int add(const std::string& n, int ci, int co, int k, int s, int act = 1) {
     convs.push_back(ConvSpec{n, ci, co, k, s, act});
     convs.back().pcin = ci;
@@ -57,6 +73,19 @@ struct ModelDef {
       add(p + ".m." + std::to_string(i) + ".cv2", c, c, 3, 1);
     }
   }
+  // C3(c1, c2, n): cv1, cv2 (c1 -> c2 / 2, 1x1, both on the block's input),
+  // cv3 (c2 -> c2, 1x1 on [bottleneck chain | cv2]), then the bottlenecks
+  // (1x1 then 3x3 at width c2 / 2) -- the state_dict order
+  void c3(const std::string& p, int c1, int c2, int n) {
+    const int c = c2 / 2;
+    add(p + ".cv1", c1, c, 1, 1);
+    add(p + ".cv2", c1, c, 1, 1);
+    add(p + ".cv3", 2 * c, c2, 1, 1);
+    for (int i = 0; i < n; ++i) {
+      add(p + ".m." + std::to_string(i) + ".cv1", c, c, 1, 1);
+      add(p + ".m." + std::to_string(i) + ".cv2", c, c, 3, 1);
+    }
+  }
   int find(const std::string& n) const {
     for (size_t i = 0; i < convs.size(); ++i)
       if (convs[i].name == n) return (int)i;
@@ -67,7 +96,7 @@ struct ModelDef {
 // false: unknown variant / dtype, or nc outside [kMinClasses, kMaxClasses]
 bool build_def(int variant, ModelDef& m, int dtype = RV_YOLO_DTYPE_BF16, int nc = 80);
 // RV_OK, or RV_EINVAL with rv_last_error naming what is wrong with
-// (variant, dtype, nc): the range of nc, fp8 with nc != 80
+// (variant, dtype, nc): the range of nc, fp8 with nc != 80 or a YOLOv5u variant
 int check_plan_args(int variant, int dtype, int nc);
 size_t packed_bytes(const ModelDef& m);
 size_t flat_floats(const ModelDef& m);

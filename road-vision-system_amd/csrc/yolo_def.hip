@@ -1,6 +1,7 @@
-// YOLOv8 model definition + weight packer (restating the Ultralytics
-// yolov8.yaml graph: Conv / C2f / SPPF / Detect(DFL)) and the C ABI entries
-// that need no handle.  Host code only.
+// YOLOv8 / YOLOv5u model definition + weight packer (restating the
+// Ultralytics yolov8.yaml graph: Conv / C2f / SPPF / Detect(DFL), and the
+// yolov5.yaml graph of the "u" models: Conv k6 / C3 / SPPF under the same
+// Detect) and the C ABI entries that need no handle.  Host code only.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,7 +16,33 @@ static bool variant_widths(int variant, Variant& v) {
   // m [0.67, 0.75, 768], l [1.00, 1.00, 512], x [1.00, 1.25, 512]
   static const double S[5][3] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 768},
                                  {1.00, 1.00, 512},  {1.00, 1.25, 512}};
-  if (variant < 0 || variant > 4) return false;
+  // yolov5.yaml scales (variants 5..9): depth, width, max channels 1024
+  static const double S5[5][3] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 1024},
+                                  {1.00, 1.00, 1024}, {1.33, 1.25, 1024}};
+  if (variant < 0 || variant >= kNumVariants) return false;
+  v.family = family_of(variant);
+  if (v.family == kFamilyV5u) {
+    const double d = S5[variant - 5][0], w = S5[variant - 5][1], mc = S5[variant - 5][2];
+    auto ch = [&](int c) { return make_div8(std::min((double)c, mc) * w); };
+    auto rep = [&](int n) { return std::max((int)std::lround(n * d), 1); };
+    v.c1 = ch(64);
+    v.c2 = ch(128);
+    v.c3 = ch(256);
+    v.c4 = ch(512);
+    v.c5 = ch(1024);
+    v.h12 = v.c3;  // model.14
+    v.h15 = v.c3;  // model.17 -> Detect P3
+    v.h18 = v.c4;  // model.20 -> Detect P4
+    v.h21 = v.c5;  // model.23 -> Detect P5
+    v.nb = rep(3);
+    v.nm = rep(6);
+    v.nx = rep(9);
+    v.c2d = std::max(std::max(16, v.h15 / 4), v.reg * 4);
+    v.c3d = std::max(v.h15, std::min(v.nc, 100));
+    v.c3p = (v.c3d + 7) & ~7;
+    v.hcs = (4 * v.reg + v.nc + 3) & ~3;
+    return true;
+  }
   const double d = S[variant][0], w = S[variant][1], mc = S[variant][2];
   auto ch = [&](int c) { return make_div8(std::min((double)c, mc) * w); };
   auto rep = [&](int n) { return std::max((int)std::lround(n * d), 1); };
@@ -38,24 +65,70 @@ static bool variant_widths(int variant, Variant& v) {
 }
 
 static size_t conv0q_bytes(int C0) { return 3 * (size_t)C0 * 64 + 20 * (size_t)C0; }
+static size_t conv0q6_bytes(int C0) { return 9 * (size_t)C0 * 64 + 20 * (size_t)C0; }
 
 int check_plan_args(int variant, int dtype, int nc) {
-  RV_CHECK_ARG(variant >= 0 && variant <= 4, "unknown variant %d", variant);
+  RV_CHECK_ARG(variant >= 0 && variant < kNumVariants, "unknown variant %d", variant);
   RV_CHECK_ARG(dtype == RV_YOLO_DTYPE_BF16 || dtype == RV_YOLO_DTYPE_FP8, "unknown dtype %d", dtype);
   RV_CHECK_ARG(nc >= kMinClasses && nc <= kMaxClasses, "nc = %d outside the supported range %d..%d",
                nc, kMinClasses, kMaxClasses);
   RV_CHECK_ARG(dtype != RV_YOLO_DTYPE_FP8 || nc == 80,
                "fp8 plans support nc = 80 only (got nc = %d): the fp8 parity rests on the 80-class "
                "calibration; use the bf16 plan", nc);
+  RV_CHECK_ARG(dtype != RV_YOLO_DTYPE_FP8 || family_of(variant) != kFamilyV5u,
+               "YOLOv5u plans (variant %d) are bf16 only: there is no fp8 YOLOv5u plan", variant);
   return RV_OK;
 }
 
-bool build_def(int variant, ModelDef& m, int dtype, int nc) {
-  if (nc < kMinClasses || nc > kMaxClasses) return false;
-  m.v.nc = nc;
-  if (!variant_widths(variant, m.v)) return false;
-  if (dtype != RV_YOLO_DTYPE_BF16 && dtype != RV_YOLO_DTYPE_FP8) return false;
-  m.dtype = dtype;
+// The Detect head (the same module in both families) on maps of widths chs
+static void add_detect(ModelDef& m, const int (&chs)[3]) {
+  const Variant& v = m.v;
+  for (int i = 0; i < 3; ++i) {
+    const std::string p = m.head + "cv2." + std::to_string(i);
+    m.add(p + ".0", chs[i], v.c2d, 3, 1);
+    m.add(p + ".1", v.c2d, v.c2d, 3, 1);
+    m.add(p + ".2", v.c2d, 4 * v.reg, 1, 1, 0);
+  }
+  for (int i = 0; i < 3; ++i) {
+    const std::string p = m.head + "cv3." + std::to_string(i);
+    // the plan runs the branch c3p wide (c3d padded to 8: 16-byte feature
+    // rows); the state_dict shapes and the packed layout keep c3d
+    m.convs[m.add(p + ".0", chs[i], v.c3d, 3, 1)].pcout = v.c3p;
+    ConvSpec& c1 = m.convs[m.add(p + ".1", v.c3d, v.c3d, 3, 1)];
+    c1.pcin = c1.pcout = v.c3p;
+    m.convs[m.add(p + ".2", v.c3d, v.nc, 1, 1, 0)].pcin = v.c3p;
+  }
+}
+
+// yolov5.yaml (the "u" models): layer numbers as in the yaml; Upsample (11,
+// 15) and Concat (12, 16, 19, 22) hold no weights
+static void build_v5u(ModelDef& m) {
+  const Variant& v = m.v;
+  m.head = "model.24.";
+  m.add("model.0", 3, v.c1, 6, 2);
+  m.add("model.1", v.c1, v.c2, 3, 2);
+  m.c3("model.2", v.c2, v.c2, v.nb);
+  m.add("model.3", v.c2, v.c3, 3, 2);
+  m.c3("model.4", v.c3, v.c3, v.nm);
+  m.add("model.5", v.c3, v.c4, 3, 2);
+  m.c3("model.6", v.c4, v.c4, v.nx);
+  m.add("model.7", v.c4, v.c5, 3, 2);
+  m.c3("model.8", v.c5, v.c5, v.nb);
+  m.add("model.9.cv1", v.c5, v.c5 / 2, 1, 1);
+  m.add("model.9.cv2", v.c5 / 2 * 4, v.c5, 1, 1);
+  m.add("model.10", v.c5, v.c4, 1, 1);
+  m.c3("model.13", 2 * v.c4, v.c4, v.nb);
+  m.add("model.14", v.c4, v.c3, 1, 1);
+  m.c3("model.17", 2 * v.c3, v.c3, v.nb);
+  m.add("model.18", v.c3, v.c3, 3, 2);
+  m.c3("model.20", 2 * v.c3, v.c4, v.nb);
+  m.add("model.21", v.c4, v.c4, 3, 2);
+  m.c3("model.23", 2 * v.c4, v.c5, v.nb);
+  add_detect(m, {v.h15, v.h18, v.h21});
+}
+
+// yolov8.yaml
+static void build_v8(ModelDef& m) {
   const Variant& v = m.v;
   m.add("model.0", 3, v.c1, 3, 2);
   m.add("model.1", v.c1, v.c2, 3, 2);
@@ -74,22 +147,21 @@ bool build_def(int variant, ModelDef& m, int dtype, int nc) {
   m.c2f("model.18", v.h15 + v.h12, v.h18, v.nb);
   m.add("model.19", v.h18, v.h18, 3, 2);
   m.c2f("model.21", v.h18 + v.c5, v.h21, v.nb);
-  const int chs[3] = {v.h15, v.h18, v.h21};
-  for (int i = 0; i < 3; ++i) {
-    const std::string p = "model.22.cv2." + std::to_string(i);
-    m.add(p + ".0", chs[i], v.c2d, 3, 1);
-    m.add(p + ".1", v.c2d, v.c2d, 3, 1);
-    m.add(p + ".2", v.c2d, 4 * v.reg, 1, 1, 0);
-  }
-  for (int i = 0; i < 3; ++i) {
-    const std::string p = "model.22.cv3." + std::to_string(i);
-    // the plan runs the branch c3p wide (c3d padded to 8: 16-byte feature
-    // rows); the state_dict shapes and the packed layout keep c3d
-    m.convs[m.add(p + ".0", chs[i], v.c3d, 3, 1)].pcout = v.c3p;
-    ConvSpec& c1 = m.convs[m.add(p + ".1", v.c3d, v.c3d, 3, 1)];
-    c1.pcin = c1.pcout = v.c3p;
-    m.convs[m.add(p + ".2", v.c3d, v.nc, 1, 1, 0)].pcin = v.c3p;
-  }
+  add_detect(m, {v.h15, v.h18, v.h21});
+}
+
+bool build_def(int variant, ModelDef& m, int dtype, int nc) {
+  if (nc < kMinClasses || nc > kMaxClasses) return false;
+  m.v.nc = nc;
+  if (!variant_widths(variant, m.v)) return false;
+  if (dtype != RV_YOLO_DTYPE_BF16 && dtype != RV_YOLO_DTYPE_FP8) return false;
+  if (dtype == RV_YOLO_DTYPE_FP8 && m.v.family == kFamilyV5u) return false;
+  m.dtype = dtype;
+  const Variant& v = m.v;
+  if (v.family == kFamilyV5u)
+    build_v5u(m);
+  else
+    build_v8(m);
   // packed layout: conv 0 keeps f32 OIHW (VALU conv), the rest bf16
   // [Cout_pad16][ky][kx][Cin_pad32]; biases f32 [Cout_pad16]; 256-B aligned.
   // fp8 plans: every conv but conv 0 and the Detect head's last 1x1 stage
@@ -100,7 +172,7 @@ bool build_def(int variant, ModelDef& m, int dtype, int nc) {
   for (size_t i = 0; i < m.convs.size(); ++i) {
     ConvSpec& c = m.convs[i];
     c.f8 = dtype == RV_YOLO_DTYPE_FP8 && i > 0 &&
-           !(c.name.compare(0, 9, "model.22.") == 0 && c.name.size() > 2 &&
+           !(c.name.compare(0, m.head.size(), m.head) == 0 && c.name.size() > 2 &&
              c.name.compare(c.name.size() - 2, 2, ".2") == 0);
     const int cop = (c.cout + 15) & ~15;
     const int cip = c.f8 ? (c.cin + 63) & ~63 : (c.cin + 31) & ~31;
@@ -115,7 +187,7 @@ bool build_def(int variant, ModelDef& m, int dtype, int nc) {
     }
   }
   m.q_off = off;
-  m.q_bytes = conv0q_bytes(m.convs[0].cout);
+  m.q_bytes = v.family == kFamilyV5u ? conv0q6_bytes(m.convs[0].cout) : conv0q_bytes(m.convs[0].cout);
   return true;
 }
 
@@ -156,6 +228,45 @@ static void pack_conv0q(const float* w, const float* b, int C0, uint8_t* dst) {
       const long long d[3] = {d0, d1, d2};
       for (int t = 0; t < 3; ++t) {
         D[((size_t)t * C0 + o) * 64 + k] = (int8_t)d[t];
+        sd[t] += d[t];
+      }
+    }
+    S[o] = s;
+    Bv[o] = b[o];
+    for (int t = 0; t < 3; ++t) Cq[t * C0 + o] = (int32_t)(128 * sd[t]);
+  }
+}
+
+// Integer form of YOLOv5u's conv 0 (k6 s2 p2; conv.h Conv0Q, yolo_def.h for
+// the layout): the rule of pack_conv0q over the 6 x 6 x 3 = 108 taps.  Window
+// row ky is 18 contiguous BGR bytes j = 3 kx + ch; rows 2p and 2p + 1 share
+// the 64-deep K block p (slots 32 (ky & 1) + j), every other slot zero.
+// |T_i| <= 108 * 128 * 255 < 2^24, so the digit sums stay exact in i32 and f32.
+static void pack_conv0q6(const float* w, const float* b, int C0, uint8_t* dst) {
+  int8_t* D = (int8_t*)dst;
+  float* S = (float*)(dst + 9 * (size_t)C0 * 64);
+  float* Bv = S + C0;
+  int32_t* Cq = (int32_t*)(Bv + C0);
+  for (int o = 0; o < C0; ++o) {
+    double V[192] = {0.0}, M = 0.0;
+    for (int ky = 0; ky < 6; ++ky)
+      for (int kx = 0; kx < 6; ++kx)
+        for (int ch = 0; ch < 3; ++ch) {
+          const double v = (double)w[((o * 3 + (2 - ch)) * 6 + ky) * 6 + kx] / 255.0;
+          V[64 * (ky / 2) + 32 * (ky & 1) + 3 * kx + ch] = v;
+          M = std::max(M, std::fabs(v));
+        }
+    const float s = M > 0.0 ? (float)(M / (127.0 * 65536.0)) : 1.0f;
+    long long sd[3] = {0, 0, 0};
+    for (int k = 0; k < 192; ++k) {
+      const long long q = std::llround(V[k] / (double)s);
+      const long long d2 = ((q + 128) & 255) - 128;
+      const long long q1 = (q - d2) / 256;
+      const long long d1 = ((q1 + 128) & 255) - 128;
+      const long long d0 = (q1 - d1) / 256;
+      const long long d[3] = {d0, d1, d2};
+      for (int t = 0; t < 3; ++t) {
+        D[((size_t)t * C0 + o) * 192 + k] = (int8_t)d[t];
         sd[t] += d[t];
       }
     }
@@ -297,7 +408,10 @@ extern "C" int rv_yolo_pack3(int variant, int dtype, int nc, const float* flat, 
     p += nw + c.cout;
     if (i == 0) {
       memcpy(out + c.w_off, w, nw * 4);
-      pack_conv0q(w, b, c.cout, out + m.q_off);
+      if (m.v.family == kFamilyV5u)
+        pack_conv0q6(w, b, c.cout, out + m.q_off);
+      else
+        pack_conv0q(w, b, c.cout, out + m.q_off);
     } else if (c.f8) {
       // per output channel: scale = 2^ceil(log2(amax / 448)), codes RNE
       const int cip = (c.cin + 63) & ~63;

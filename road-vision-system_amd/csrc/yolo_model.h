@@ -93,6 +93,10 @@ struct Resume {  // where a forward part stopped: what the next part must contin
   const void* ws = nullptr;
 };
 
+// YOLOv5nu's fused k6 stem (conv0-k6 + model.1): the default of
+// RV_YOLO_OPT_STEM6_FUSED, set by the measurement in DESIGN.md "YOLOv5u"
+constexpr int kStem6FusedDefault = 1;
+
 struct Model {
   ModelDef def;
   Profile prof;
@@ -139,6 +143,7 @@ struct Model {
   int fuse_cv1 = 1;                // RV_YOLO_OPT_FUSE_CV1
   int c2f_tap_pairs = 1;           // RV_YOLO_OPT_C2F_TAP_PAIRS
   int head_sparse = 2;             // RV_YOLO_OPT_HEAD_SPARSE: 0 dense, 1 sparse, 2 auto
+  int stem6_fused = kStem6FusedDefault;  // RV_YOLO_OPT_STEM6_FUSED
   // decode form of the last forward that reached the decode (rv_yolo_head_form;
   // -1 before one): 0 unfused last stage, 1 fused + LDS class scan, 2 fused
   // with register-resident class scores, 3 the class-only form 2 followed by
@@ -161,6 +166,11 @@ struct Model {
   // buffer ids
   int X0, X1, C2, X2, X3, C4, CAT14, X5, C6, CAT11, X7, C8, X8, SP, CAT20, C12, CAT17, C15,
       X15, C18, X18, C21, X21;
+  // YOLOv5u plans: the outputs of model.4 / 6 / 9 / 13 (P3, P4, SPPF and the
+  // top-down P4 block), which no concat buffer holds there; CAT14 and CAT11
+  // are -1 (both Upsample + Concat pairs are virtual), CAT17 / CAT20 are the
+  // yaml's concats 19 / 22 and X15 / X18 / X21 the Detect inputs 17 / 20 / 23
+  int X4 = -1, X6 = -1, X9 = -1, X13 = -1;
   int DA[3], DB[3], HD[3];
 
   // byte offset of every buffer in a workspace for batch B (256-B aligned),

@@ -1,4 +1,4 @@
-"""YOLOv8 weights for the HIP detector.
+"""YOLOv8 and YOLOv5u weights for the HIP detector.
 
 The conv list (names, shapes, order) comes from the native plan in
 csrc/yolo_def.hip (rv_yolo_conv_info) -- Ultralytics state_dict order with BN
@@ -26,11 +26,20 @@ The class count is the checkpoint's own (the first dimension of
 takes it from the checkpoint; ``detect.nc`` may state it and must then agree,
 ``detect.names`` names the classes (names_from_config).  Synthetic weights
 exist for 80 classes only.
+
+YOLOv5u (``yolov5n.pt`` ... ``yolov5xu.pt``: Ultralytics resolves the plain
+YOLOv5 names to the anchor-free "u" re-release, yolov5.yaml under the YOLOv8
+Detect head) is variants 5..9.  Its Detect module is ``model.24``, so the
+class count is read from ``model.24.cv3.0.2.weight``.  There is no shipped
+calibration and no fp8 plan for it: it needs a ``detect.weights`` file and
+runs in bf16.  An anchor-based checkpoint of the original yolov5 repository
+(``model.24.m.*`` / ``model.24.anchors``) is a different network and refused.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -51,22 +60,51 @@ COCO80 = [
     "teddy bear", "hair drier", "toothbrush"]
 
 
+V5U_VARIANTS = {"n": 5, "s": 6, "m": 7, "l": 8, "x": 9}  # YOLOv5u (include/rvhip.h)
+_V5U_NAME = re.compile(r"yolov5([nsmlx])u?(\.[a-z0-9]+)?$")
+
+
 def variant_of(model_name: str) -> int:
-    """'yolov8n.pt' -> 0 ... (the reference's cfg['model'], default.yaml:39)."""
+    """'yolov8n.pt' -> 0 ..., 'yolov5n.pt' / 'yolov5nu.pt' -> 5 ... (the
+    reference's cfg['model'], default.yaml:39; Ultralytics resolves the plain
+    YOLOv5 names to the "u" checkpoints).  The P6 models (yolov5n6u.pt) and
+    every other family raise."""
     base = os.path.basename(str(model_name)).lower()
     for k, v in VARIANTS.items():
         if base.startswith(f"yolov8{k}"):
             return v
-    raise ValueError(f"unsupported model '{model_name}' (YOLOv8 n/s/m/l/x only)")
+    m = _V5U_NAME.match(base)
+    if m:
+        return V5U_VARIANTS[m.group(1)]
+    raise ValueError(f"unsupported model '{model_name}' (YOLOv8 n/s/m/l/x and YOLOv5u "
+                     "n/s/m/l/x -- yolov5n.pt / yolov5nu.pt ... -- only)")
+
+
+def is_v5u(variant: int) -> bool:
+    return int(variant) >= 5
+
+
+def family_name(variant: int) -> str:
+    return "YOLOv5u" if is_v5u(variant) else "YOLOv8"
+
+
+def head_prefix(variant: int) -> str:
+    """State_dict prefix of the Detect module: layer 22 of yolov8.yaml, 24 of yolov5.yaml."""
+    return "model.24." if is_v5u(variant) else "model.22."
 
 
 NC_MIN, NC_MAX = 1, 128  # class counts the native plan supports (include/rvhip.h)
 CLS_KEY = "model.22.cv3.0.2.weight"  # its first dimension is the checkpoint's class count
 
 
+def cls_key(variant: int = None) -> str:
+    """CLS_KEY of the variant's family (YOLOv8 without a variant)."""
+    return CLS_KEY if variant is None else head_prefix(variant) + "cv3.0.2.weight"
+
+
 def conv_list(variant: int, nc: int = 80) -> List[Tuple[str, int, int, int, int, int]]:
     """[(name, cin, cout, k, stride, silu)] in packing order: the Ultralytics
-    state_dict shapes of a YOLOv8 with `nc` classes."""
+    state_dict shapes of a YOLOv8 / YOLOv5u with `nc` classes."""
     lib = _lib.load()
     out = []
     info = (ctypes.c_int * 5)()
@@ -126,6 +164,10 @@ def synthetic_weights(variant: int, seed: int = 0, nc: int = 80) -> np.ndarray:
     tests/golden/make_yolo_scales.py), so every conv's pre-activation is O(1)
     like a trained model's fused BN output and a road frame yields a few
     hundred NMS candidates."""
+    if is_v5u(variant):
+        raise ValueError(f"no synthetic calibration for YOLOv5u (variant {variant}) in "
+                         f"{os.path.basename(_CALIB)}: a YOLOv5u model needs a detect.weights "
+                         "file (a local state_dict of the 'u' checkpoint)")
     if int(nc) != 80:
         raise ValueError(f"no synthetic calibration for nc = {nc} in {os.path.basename(_CALIB)} "
                          "(the shipped calibration is 80-class); a model with a custom class "
@@ -194,25 +236,43 @@ def _strip_prefix(t: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     return t
 
 
-def nc_of_state_dict(tensors: Dict[str, np.ndarray]) -> int:
+def nc_of_state_dict(tensors: Dict[str, np.ndarray], variant: int = None) -> int:
     """The class count of an Ultralytics DetectionModel state_dict: the first
     dimension of model.22.cv3.0.2.weight (a plain nn.Conv2d, so the key is the
-    same before and after model.fuse(), with or without the "model." nesting)."""
+    same before and after model.fuse(), with or without the "model." nesting);
+    with a YOLOv5u `variant`, of model.24.cv3.0.2.weight."""
     t = _strip_prefix(tensors)
-    if CLS_KEY not in t:
-        raise KeyError(f"{CLS_KEY}: not in the state_dict (the class count is read from it)")
-    nc = int(np.asarray(t[CLS_KEY]).shape[0])
+    key = cls_key(variant)
+    if key not in t:
+        raise KeyError(f"{key}: not in the state_dict (the class count is read from it)")
+    nc = int(np.asarray(t[key]).shape[0])
     if not NC_MIN <= nc <= NC_MAX:
-        raise ValueError(f"{CLS_KEY} has {nc} classes: outside the supported range "
+        raise ValueError(f"{key} has {nc} classes: outside the supported range "
                          f"{NC_MIN}..{NC_MAX}")
     return nc
+
+
+def check_family(t: Dict[str, np.ndarray], variant: int) -> None:
+    """Refuse a state_dict that is not of `variant`'s family: an anchor-based
+    YOLOv5 checkpoint (the original yolov5 repository's Detect: model.24.m.* /
+    model.24.anchors), or the other supported family (recognised by its
+    Detect module's layer number)."""
+    if any(k.startswith("model.24.m.") or k.startswith("model.24.anchor") for k in t):
+        raise ValueError("the state_dict is an anchor-based YOLOv5 checkpoint of the original "
+                         "yolov5 repository (it has model.24.m.* / model.24.anchors): a different "
+                         "network; the anchor-free 'u' checkpoint (yolov5nu.pt ...) is needed")
+    other = 0 if is_v5u(variant) else 5  # any variant of the other family
+    if cls_key(variant) not in t and cls_key(other) in t:
+        raise ValueError(f"the state_dict is a {family_name(other)} one (Detect at "
+                         f"{head_prefix(other)[:-1]}) but detect.model names a "
+                         f"{family_name(variant)} model (Detect at {head_prefix(variant)[:-1]})")
 
 
 def _shaped(t: Dict[str, np.ndarray], key: str, shape, variant: int, nc: int) -> np.ndarray:
     a = np.asarray(t[key], np.float32)
     if a.size != int(np.prod(shape)):
-        raise ValueError(f"{key}: shape {tuple(a.shape)} does not fit YOLOv8 variant {variant} "
-                         f"with nc = {nc} (expected {tuple(shape)})")
+        raise ValueError(f"{key}: shape {tuple(a.shape)} does not fit {family_name(variant)} "
+                         f"variant {variant} with nc = {nc} (expected {tuple(shape)})")
     return a.reshape(shape)
 
 
@@ -223,10 +283,11 @@ def flat_from_state_dict(tensors: Dict[str, np.ndarray], variant: int, nc: int =
     class count is the checkpoint's own (nc_of_state_dict); an `nc` that
     disagrees with it is an error.  return_nc: (flat, nc) instead of flat."""
     t = _strip_prefix(tensors)
-    have = nc_of_state_dict(t)
+    check_family(t, variant)
+    have = nc_of_state_dict(t, variant if is_v5u(variant) else None)
     if nc is not None and int(nc) != have:
         raise ValueError(f"detect.nc = {int(nc)} but the checkpoint has {have} classes "
-                         f"({CLS_KEY} has {have} rows)")
+                         f"({cls_key(variant)} has {have} rows)")
     nc = have
     parts = []
     for name, cin, cout, k, s, act in conv_list(variant, nc):
@@ -268,6 +329,12 @@ def check_fp8_nc(dtype: str, nc: int) -> None:
                          "rests on the 80-class calibration; run a custom class count in bf16")
 
 
+def check_fp8_variant(dtype: str, variant: int) -> None:
+    if dtype == "fp8" and is_v5u(variant):
+        raise ValueError(f"dtype 'fp8' is not available for YOLOv5u (variant {int(variant)}): "
+                         "its plans are bf16 only; set detect.dtype to bf16")
+
+
 def pack(variant: int, flat: np.ndarray, dtype: str = "bf16", nc: int = 80) -> np.ndarray:
     """Device layout as a u8 host array: bf16 [Cout16][ky][kx][Cin32] + f32
     bias, or (dtype 'fp8', nc = 80 only) OCP e4m3 [Cout16][ky][kx][Cin64] +
@@ -276,6 +343,7 @@ def pack(variant: int, flat: np.ndarray, dtype: str = "bf16", nc: int = 80) -> n
     lib = _lib.load()
     dt = DTYPES[dtype]
     check_fp8_nc(dtype, nc)
+    check_fp8_variant(dtype, variant)
     flat = np.ascontiguousarray(flat, np.float32)
     nbytes = lib.rv_yolo_packed_bytes3(variant, dt, int(nc))
     out = np.zeros(nbytes, np.uint8)
@@ -299,6 +367,10 @@ def detector_weights(det_cfg: dict, variant: int) -> Tuple[np.ndarray, int]:
     nc = det_cfg.get("nc")
     if w and str(w).lower() != "synthetic":
         return load_weights(str(w), variant, nc, return_nc=True)
+    if is_v5u(variant):
+        raise ValueError(f"detect.model={det_cfg.get('model')!r} is a YOLOv5u model and there is "
+                         "no shipped synthetic calibration for it: set detect.weights to a local "
+                         "state_dict of the 'u' checkpoint")
     if not w:
         warnings.warn(f"detect.model={det_cfg.get('model', 'yolov8n.pt')!r} but no detect.weights "
                       "file is configured: using seeded SYNTHETIC weights (set detect.weights to "

@@ -22,7 +22,8 @@ from .. import _lib, kernels
 from .._lib import call, ptr, stream_ptr
 from .base import Detector
 from .types import Detection
-from .weights import (COCO80, DTYPES, NC_MAX, NC_MIN, check_fp8_nc, detector_weights,
+from .weights import (COCO80, DTYPES, NC_MAX, NC_MIN, check_fp8_nc, check_fp8_variant,
+                      detector_weights,
                       names_from_config, pack, variant_of)
 
 CAND_BYTES = 32
@@ -31,6 +32,7 @@ CAND_BYTES = 32
 OPT_RAW_UNFUSED, OPT_FUSE_C2F, OPT_STEM_X1, OPT_HEAD_STREAMS, OPT_FUSE_CV1 = 1, 2, 3, 4, 5
 OPT_C2F_TAP_PAIRS = 7
 OPT_HEAD_SPARSE = 8
+OPT_STEM6_FUSED = 9
 
 
 def scale_boxes_params(img1_hw, img0_hw):
@@ -100,6 +102,7 @@ class YoloEngine:
         if not NC_MIN <= self.nc <= NC_MAX:
             raise ValueError(f"nc = {nc} outside the supported range {NC_MIN}..{NC_MAX}")
         check_fp8_nc(dtype, self.nc)
+        check_fp8_variant(dtype, variant)
         self.flat = flat_weights
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         self.max_batch = int(max_batch)
@@ -266,6 +269,12 @@ class YoloEngine:
         hidden-width-16 chains only (default), 2 = widths 16 and 32,
         False / 0 = none."""
         self._set_option(OPT_FUSE_C2F, 1 if on is True else (0 if on is False else int(on)))
+
+    def set_stem6_fused(self, on: bool) -> None:
+        """YOLOv5nu: model.0 (k6) + model.1 as one kernel with the P1 map in
+        LDS (RV_YOLO_OPT_STEM6_FUSED; X1 bit-identical to the two launches);
+        raw parity forwards run the two launches either way."""
+        self._set_option(OPT_STEM6_FUSED, 1 if on else 0)
 
     def set_head_sparse(self, mode) -> None:
         """The Detect box branch behind cv2.i.0 at the candidates only
