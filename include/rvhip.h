@@ -320,6 +320,59 @@ int rv_conv_bf16(const void* in, int B, int Hin, int Win, int Cin, int in_cs, co
                  const void* res, int res_cs, int act, const int* cfg6, void* stream);
 int rv_yolo_set_option(void* handle, int opt, int value);
 
+/* --- YOLO11 (yolo11.yaml: Conv / C3k2 / SPPF / C2PSA, Detect at model.23
+ * with a depthwise-separable class branch).  variant: 20=n 21=s 22=m 23=l
+ * 24=x.  Variants 10..19 are no variant: every entry returns RV_EINVAL (the
+ * size_t entries 0) for them.  YOLO11 plans are bf16 only (RV_YOLO_DTYPE_FP8
+ * with a variant >= 20: RV_EINVAL), class counts 1..128 as for YOLOv8.  The
+ * first conv is YOLOv8's (k3 s2 on i8 MFMAs).  The Detect head is dense only:
+ * RV_YOLO_OPT_HEAD_SPARSE has no effect on these plans and rv_yolo_head_form
+ * never reports 3 for them; no launch of a YOLO11 forward is fused.
+ *
+ * A depthwise conv (the class branch's DWConv 3x3, the attention's `pe`) is a
+ * conv of the list like any other: rv_yolo_conv_info reports cin = cout = C,
+ * its flat weights are the state_dict's [C][1][3][3] then bias[C], and
+ * rv_yolo_conv_groups returns C for it (1 for a dense conv; RV_EINVAL for a
+ * bad variant / nc / index).  Packed: bf16 [ky * 3 + kx][C_pad8], f32 bias. */
+int rv_yolo_conv_groups(int variant, int nc, int idx);
+
+/* One depthwise 3x3 conv (stride 1, zero pad 1) on bf16 NHWC maps: per
+ * channel c, out = act(bias[c] + sum w[ky * 3 + kx][c] in[y + ky - 1][x + kx - 1][c])
+ * (+ res), f32 accumulation in the order bias, ky 0..2, kx 0..2 inside, SiLU
+ * when act != 0, the optional bf16 residual added after the activation, one
+ * rounding to bf16.  w: bf16 [9][C], bias: f32 [C].
+ *
+ * in / out / res are views (pointer to pixel 0 of the wide tensor, its
+ * channel count *_cs, the view's first channel *_co).  The input view may be
+ * grouped: with in_gw > 0, logical channel c is channel in_co + (c / in_gw) *
+ * in_gs + c % in_gw of the wide tensor (the v part of a qkv map: in_gw 64,
+ * in_gs 128, in_co 64); in_gw = in_gs = 0: channels [in_co, in_co + C).
+ * Checked before anything is launched (RV_EINVAL otherwise, nothing written):
+ * C a positive multiple of 8; every *_cs, *_co, in_gw, in_gs a multiple of 8
+ * and every pointer 16-byte aligned (16-byte accesses of 8 channels); C %
+ * in_gw == 0, in_gs >= in_gw; each view's channels inside its *_cs; B and
+ * ceil(H / 8) at most 65535.  Only the view's channels are read or written. */
+int rv_dwconv3x3_bf16(const void* in, int B, int H, int W, int C, int in_cs, int in_co, int in_gw,
+                      int in_gs, const void* w, const float* bias, void* out, int out_cs,
+                      int out_co, const void* res, int res_cs, int res_co, int act, void* stream);
+
+/* Multi-head self-attention of a PSA block (key_dim 32, head_dim 64) over the
+ * N positions of each of B images, all images and heads in one launch.  qkv:
+ * bf16 view of B * N rows of qkv_cs channels; head h reads channels qkv_co +
+ * 128 h + [0, 32) as q, [32, 64) as k, [64, 128) as v.  Per image and head
+ * S = q^T k * 32^-1/2 in f32 (the scale multiplies the f32 scores), the row
+ * maximum is subtracted, P = softmax over the keys (f32 denominator, P
+ * rounded to bf16 only as the P v operand), o = P v written as bf16 to channel
+ * out_co + 64 h + d of the output view (B * N rows of out_cs channels).  One
+ * code path for every N: 32-key tiles with online rescaling, tail keys
+ * masked.  Checked before anything is launched (RV_EINVAL otherwise, nothing
+ * written): B, N, heads >= 1 (B, heads <= 65535); qkv_co + 128 heads <=
+ * qkv_cs, out_co + 64 heads <= out_cs; qkv_cs, qkv_co multiples of 8 and qkv
+ * 16-byte aligned; out_cs, out_co multiples of 4 and out 8-byte aligned.
+ * Nothing outside those rows and channels is read or written. */
+int rv_psa_attention_bf16(const void* qkv, int B, int N, int heads, int qkv_cs, int qkv_co,
+                          void* out, int out_cs, int out_co, void* stream);
+
 /* fp8 plans (BASELINE configs[4]: "YOLOv8m 1280x1280 fp8 MFMA conv path").
  * dtype RV_YOLO_DTYPE_FP8: every conv except conv 0 (f32 weights, u8 input)
  * and the Detect head's last 1x1 stage (bf16, inside the decode) runs on
@@ -424,6 +477,18 @@ int rv_yolo_forward_part(void* handle, const uint8_t* lb, int B, void* ws, size_
 int rv_yolo_num_buffers(void* handle);
 int rv_yolo_buffer_info(void* handle, int B, int buf, int* info, size_t* off_bytes);
 int rv_yolo_trace(void* handle, int* recs, int max_recs);
+/* YOLO11 plans: a depthwise conv appears in rv_yolo_trace as a conv; its
+ * virtual-concat fields carry the input view's group form instead (in2 buf
+ * -1, in2 cs = group stride, split = group width; both 0: contiguous
+ * channels) -- attn.pe reads v of its qkv map as {co 64, width 64, stride
+ * 128}.  The attention launches of the last forward are reported here, 9 ints
+ * each in launch order: qkv view {buf, cs, co}, heads, H, W, output view {buf,
+ * cs, co} (rv_psa_attention_bf16 over N = H * W).  Returns the record count
+ * (0 for the other families).  Depthwise and attention launches keep a launch
+ * index of their own: rv_yolo_conv_candidates reports 0 configurations for
+ * them, the autotuner skips them, and rv_yolo_profile times them in their
+ * index's slot (an attention under its block's attn.qkv conv index). */
+int rv_yolo_attn_trace(void* handle, int* recs, int max_recs);
 
 /* Live device timing of the conv launches (HIP events recorded on the launch
  * stream around every conv_mfma launch of the next max_forwards forwards;

@@ -45,6 +45,8 @@ struct ConvArgs {
   // candidate inside the sparse box-branch kernel (head_box.hip).  It keeps
   // its launch index so the per-index tuned configurations stay aligned
   // between dense and sparse forwards of a handle.
+  // -2 / -3: a depthwise conv / an attention launch of a YOLO11 plan, run by
+  // their own kernels (dwconv.hip, attn.hip); placeholders for the same reason.
   int fused;
   // fp8 (OCP e4m3fn) path: in8 = 1 -> the input (and residual) views hold
   // fp8 codes with per-tensor scales s_in / s_res (value = code * s), the
@@ -159,6 +161,18 @@ struct C2fArgs {
 };
 bool c2f_fusable(int C, int N, int cat_cs, int cat_co, int out_cs, int out_co);
 int launch_c2f_chain(const C2fArgs& a, int C, int N, bool shortcut, hipStream_t s);
+
+// Depthwise 3x3 conv, stride 1, zero pad 1 (dwconv.hip): views as above; the
+// input view in the group form when in_gw > 0 (in_gw channels every in_gs
+// from in_co); w bf16 [9][C], bias f32 [C]; SiLU when act; + res after it.
+int launch_dwconv3x3(const bf16_t* in, int in_cs, int in_co, int in_gw, int in_gs, const bf16_t* w,
+                     const float* bias, int B, int H, int W, int C, int act, const bf16_t* res,
+                     int res_cs, int res_co, bf16_t* out, int out_cs, int out_co, hipStream_t s);
+
+// PSA self-attention (attn.hip): per image and head softmax(q^T k 32^-1/2) v
+// over N positions; qkv rows [q 32 | k 32 | v 64] per head, o 64 per head.
+int launch_psa_attention(const bf16_t* qkv, int B, int N, int heads, int qkv_cs, int qkv_co,
+                         bf16_t* out, int out_cs, int out_co, hipStream_t s);
 
 struct HeadLevel {
   const float* logits;  // [B][H][W][cs] f32: [0,4*reg) box bins, [4*reg, 4*reg+nc) classes,

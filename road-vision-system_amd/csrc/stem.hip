@@ -168,6 +168,9 @@ static int launch_conv0_t(const uint8_t* img, int B, int H, int W, const Conv0Q&
     case 48: conv0_kernel<3, F8><<<blocks, 256, 0, s>>>(img, B, H, W, q, out, out_cs, s_out); break;
     case 64: conv0_kernel<4, F8><<<blocks, 256, 0, s>>>(img, B, H, W, q, out, out_cs, s_out); break;
     case 80: conv0_kernel<5, F8><<<blocks, 256, 0, s>>>(img, B, H, W, q, out, out_cs, s_out); break;
+    case 96:  // YOLO11x
+      conv0_kernel<6, F8><<<blocks, 256, 0, s>>>(img, B, H, W, q, out, out_cs, s_out);
+      break;
     default:
       set_error("conv0 C0=%d unsupported", C0);
       return RV_EINVAL;

@@ -1,4 +1,4 @@
-// YOLOv8 / YOLOv5u model plan + forward (the detector backend behind
+// YOLOv8 / YOLOv5u / YOLO11 model plan + forward (the detector backend behind
 // src/detect/yolo_ultralytics.py:7-53; the model definition and the weight
 // packer are in yolo_def.hip).
 //
@@ -76,6 +76,91 @@ static void plan_v5u(Model& M) {
     }
 }
 
+// The C3k2 blocks of a YOLO11 plan: state_dict prefix, map level, hidden
+// width c (= int(c2 e)) and whether the block nests C3k
+struct C3k2Def {
+  const char* p;
+  int level, c;
+  bool c3k;
+};
+static std::vector<C3k2Def> c3k2_blocks(const Variant& v) {
+  return {{"model.2", 2, v.c3 / 4, v.c3k},  {"model.4", 3, v.c4 / 4, v.c3k},
+          {"model.6", 4, v.c4 / 2, true},   {"model.8", 5, v.c5 / 2, true},
+          {"model.13", 4, v.h12 / 2, v.c3k}, {"model.16", 3, v.h15 / 2, v.c3k},
+          {"model.19", 4, v.h18 / 2, v.c3k}, {"model.22", 5, v.h21 / 2, true}};
+}
+
+// YOLO11 (yolo11.yaml): one buffer per activation.  A C3k2 block's concat
+// buffer C<n> holds [y0 | y1 | m.0's output | ...] as a C2f's; "prefix.m.i"
+// is bottleneck i's hidden map (width c / 2), and for a nested C3k
+// "prefix.m.i.t.j" the input of its bottleneck j (t.0 = its cv1's output),
+// "prefix.m.i.m.j" that bottleneck's hidden map and "prefix.m.i.cat" its
+// [chain | cv2] concat.  C2PSA: "PA" = cv1's output [a | b]; per PSA block
+// "model.10.m.i.qkv", ".o" (the attention output), ".ope" (o + pe(v)), ".x"
+// (b + proj), ".f" (ffn.0) and ".b" (x + ffn.1: the block's output); cv2 reads
+// [a | last b] as a virtual concat into CAT20 (the yaml's concat 21 = [model.20
+// | model.10]); CAT17 is concat 18 = [model.17 | model.13].  Concats 12 and 15
+// (behind the two Upsamples) are never materialised.  "DW<i>a" / "DW<i>b" are
+// the outputs of the Detect class branch's two depthwise convs at level i.
+static void plan_v11(Model& M) {
+  const Variant& v = M.def.v;
+  const int n = v.nb;
+  M.CAT14 = M.CAT11 = -1;
+  M.X0 = M.newbuf("X0", 1, v.c1);
+  M.X1 = M.newbuf("X1", 2, v.c2);
+  M.C2 = M.newbuf("C2", 2, (2 + n) * (v.c3 / 4));
+  M.X2 = M.newbuf("X2", 2, v.c3);
+  M.X3 = M.newbuf("X3", 3, v.c3);
+  M.C4 = M.newbuf("C4", 3, (2 + n) * (v.c4 / 4));
+  M.X4 = M.newbuf("X4", 3, v.c4);
+  M.X5 = M.newbuf("X5", 4, v.c4);
+  M.C6 = M.newbuf("C6", 4, (2 + n) * (v.c4 / 2));
+  M.X6 = M.newbuf("X6", 4, v.c4);
+  M.X7 = M.newbuf("X7", 5, v.c5);
+  M.C8 = M.newbuf("C8", 5, (2 + n) * (v.c5 / 2));
+  M.X8 = M.newbuf("X8", 5, v.c5);
+  M.SP = M.newbuf("SP", 5, 4 * (v.c5 / 2));
+  M.X9 = M.newbuf("X9", 5, v.c5);
+  M.newbuf("PA", 5, v.c5);
+  for (int i = 0; i < n; ++i) {
+    const std::string q = "model.10.m." + std::to_string(i);
+    M.newbuf(q + ".qkv", 5, v.c5);
+    M.newbuf(q + ".o", 5, v.c5 / 2);
+    M.newbuf(q + ".ope", 5, v.c5 / 2);
+    M.newbuf(q + ".x", 5, v.c5 / 2);
+    M.newbuf(q + ".f", 5, v.c5);
+    M.newbuf(q + ".b", 5, v.c5 / 2);
+  }
+  M.CAT20 = M.newbuf("CAT20", 5, v.h18 + v.c5);
+  M.C12 = M.newbuf("C12", 4, (2 + n) * (v.h12 / 2));
+  M.CAT17 = M.newbuf("CAT17", 4, v.h15 + v.h12);
+  M.C15 = M.newbuf("C15", 3, (2 + n) * (v.h15 / 2));
+  M.X15 = M.newbuf("X15", 3, v.h15);
+  M.C18 = M.newbuf("C18", 4, (2 + n) * (v.h18 / 2));
+  M.X18 = M.newbuf("X18", 4, v.h18);
+  M.C21 = M.newbuf("C21", 5, (2 + n) * (v.h21 / 2));
+  M.X21 = M.newbuf("X21", 5, v.h21);
+  plan_heads(M);
+  const int chs[3] = {v.h15, v.h18, v.h21};
+  for (int i = 0; i < 3; ++i) {
+    M.newbuf("DW" + std::to_string(i) + "a", 3 + i, chs[i]);
+    M.newbuf("DW" + std::to_string(i) + "b", 3 + i, v.c3p);
+  }
+  for (const C3k2Def& c : c3k2_blocks(v))
+    for (int i = 0; i < n; ++i) {
+      const std::string q = std::string(c.p) + ".m." + std::to_string(i);
+      if (!c.c3k) {
+        M.newbuf(q, c.level, c.c / 2);
+        continue;
+      }
+      M.newbuf(q + ".cat", c.level, c.c);
+      for (int j = 0; j < 2; ++j) {
+        M.newbuf(q + ".t." + std::to_string(j), c.level, c.c / 2);
+        M.newbuf(q + ".m." + std::to_string(j), c.level, c.c / 2);
+      }
+    }
+}
+
 static void plan(Model& M) {
   const Variant& v = M.def.v;
   for (int i = 0; i < 6; ++i) {
@@ -83,6 +168,7 @@ static void plan(Model& M) {
     M.map_w[i] = M.W >> i;
   }
   if (v.family == kFamilyV5u) return plan_v5u(M);
+  if (v.family == kFamilyV11) return plan_v11(M);
   M.X0 = M.newbuf("X0", 1, v.c1);
   M.X1 = M.newbuf("X1", 2, v.c2);
   M.C2 = M.newbuf("C2", 2, (2 + v.nb) * (v.c2 / 2));
@@ -495,7 +581,163 @@ struct Exec {
     conv(p + ".cv2", {io.in, li, View{cb, 2 * c, c}, 0, NO_VIEW, 0, NO_VIEW, io.vin});
     conv(p + ".cv3", {View{cb, 2 * c, 0}, li, io.o0, io.up0, io.o1, io.up1});
   }
+
+  // A launch that is no conv-launcher launch (a depthwise conv, an attention):
+  // it keeps a launch index -- a placeholder in the launch list (ConvArgs::fused
+  // = -2 depthwise, -3 attention) that the autotuner skips, so the per-index
+  // tuned configurations stay aligned -- and is timed in that index's slot.
+  template <class F>
+  void other_launch(ConvArgs a, int kind, int conv, double flops, double bytes, F&& run) {
+    const int li_ = M->li_base + (int)M->launches.size();
+    a.fused = kind;
+    M->launches.push_back(a);
+    status = M->prof.timed(li_, s, conv, flops, bytes, run);
+  }
+
+  // Depthwise 3x3 conv `name` (dwconv.hip): input view `in` at map li -- with
+  // gw > 0 in the group form, gw channels every gs -- -> o0, + res.  Its trace
+  // record is a conv's; the virtual-concat fields carry the group form
+  // (in2 = {-1, gs, 0}, split = gw).
+  void dw(const std::string& name, View in, int gw, int gs, int li, View o0, View res = NO_VIEW) {
+    if (status) return;
+    const ConvSpec* c = spec(name);
+    if (!c) return;
+    const int H = M->map_h[li], W = M->map_w[li], C = c->pcout;
+    M->trace.push_back(TraceRec{index(*c), in, H, W, H, W, o0, 0, NO_VIEW, 0, res, 0,
+                                View{-1, gs, 0}, gw});
+    const double px = (double)B * H * W;
+    other_launch(args(*c, {in, li, o0, 0, NO_VIEW, 0, res}), -2, index(*c), 2.0 * px * C * 9,
+                 2.0 * px * C * (res.buf >= 0 ? 3 : 2) + 2.0 * 9 * C, [&] {
+                   return launch_dwconv3x3((const bf16_t*)ptr(in.buf), in.cs, in.co, gw, gs, wptr(*c),
+                                           bptr(*c), B, H, W, C, c->act,
+                                           res.buf >= 0 ? (const bf16_t*)ptr(res.buf) : nullptr,
+                                           res.cs, res.co, (bf16_t*)ptr(o0.buf), o0.cs, o0.co, s);
+                 });
+  }
+
+  // Self-attention over the level-li map (attn.hip): qkv view -> o.  `conv`:
+  // the block's attn.qkv conv, under whose index the launch is profiled.
+  void attn(View qkv, int heads, int li, View o, int conv) {
+    if (status) return;
+    const int H = M->map_h[li], W = M->map_w[li];
+    const double N = (double)H * W;
+    M->attn_trace.push_back(AttnRec{qkv, heads, H, W, o});
+    ConvArgs a = {};
+    a.B = B;
+    other_launch(a, -3, conv, 2.0 * B * heads * N * N * (32 + 64), 2.0 * B * N * heads * (128 + 64),
+                 [&] {
+                   return launch_psa_attention((const bf16_t*)ptr(qkv.buf), B, H * W, heads, qkv.cs,
+                                               qkv.co, (bf16_t*)ptr(o.buf), o.cs, o.co, s);
+                 });
+  }
+
+  // C3k2(prefix), YOLO11: a C2f over the concat buffer cb ((2 + n) c wide)
+  // whose m.i is a bottleneck with hidden width c / 2 (3x3, 3x3, shortcut) or,
+  // with c3k, a C3k: cv1 -> two bottlenecks at width c / 2 -> [chain | cv2] ->
+  // cv3.  One launch per conv (plan_v11 names the buffers).
+  void c3k2(const std::string& p, const ConvIO& io, int cb, int c, int n, bool c3k) {
+    const int li = io.li, cs = (2 + n) * c, h = c / 2;
+    conv(p + ".cv1", {io.in, li, View{cb, cs, 0}, 0, NO_VIEW, 0, NO_VIEW, io.vin});
+    for (int i = 0; i < n; ++i) {
+      const std::string q = p + ".m." + std::to_string(i);
+      const View bin{cb, cs, (1 + i) * c}, bout{cb, cs, (2 + i) * c};
+      if (!c3k) {
+        const View tmp{M->buf_of(q), h, 0};
+        conv(q + ".cv1", {bin, li, tmp});
+        conv(q + ".cv2", {tmp, li, bout, 0, NO_VIEW, 0, bin});
+        continue;
+      }
+      const int cat = M->buf_of(q + ".cat");
+      auto tb = [&](int j) { return View{M->buf_of(q + ".t." + std::to_string(j)), h, 0}; };
+      conv(q + ".cv1", {bin, li, tb(0)});
+      for (int j = 0; j < 2; ++j) {
+        const std::string r = q + ".m." + std::to_string(j);
+        const View tmp{M->buf_of(r), h, 0};
+        conv(r + ".cv1", {tb(j), li, tmp});
+        conv(r + ".cv2", {tmp, li, j == 0 ? tb(1) : View{cat, 2 * h, 0}, 0, NO_VIEW, 0, tb(j)});
+      }
+      conv(q + ".cv2", {bin, li, View{cat, 2 * h, h}});
+      conv(q + ".cv3", {View{cat, 2 * h, 0}, li, bout});
+    }
+    conv(p + ".cv2", {View{cb, cs, 0}, li, io.o0, io.up0, io.o1, io.up1});
+  }
+
+  // C2PSA(prefix), YOLO11: cv1 -> [a | b]; n PSA blocks on b (b += proj(attn(b)
+  // + pe(v)), b += ffn(b)); cv2 on [a | b] (a virtual concat) -> out
+  void c2psa(const std::string& p, View in, int li, View out, int n) {
+    const int c = M->def.v.c5 / 2, heads = c / 64, pa = M->buf_of("PA");
+    conv(p + ".cv1", {in, li, View{pa, 2 * c, 0}});
+    View b{pa, 2 * c, c};
+    for (int i = 0; i < n && !status; ++i) {
+      const std::string q = p + ".m." + std::to_string(i);
+      const View qkv{M->buf_of(q + ".qkv"), 2 * c, 0}, o{M->buf_of(q + ".o"), c, 0},
+          ope{M->buf_of(q + ".ope"), c, 0}, x{M->buf_of(q + ".x"), c, 0},
+          f{M->buf_of(q + ".f"), 2 * c, 0}, bo{M->buf_of(q + ".b"), c, 0};
+      conv(q + ".attn.qkv", {b, li, qkv});
+      attn(qkv, heads, li, o, M->def.find(q + ".attn.qkv"));
+      // pe on v (64 channels of every head's 128, in o's channel order), + o
+      dw(q + ".attn.pe", View{qkv.buf, 2 * c, 64}, 64, 128, li, ope, o);
+      conv(q + ".attn.proj", {ope, li, x, 0, NO_VIEW, 0, b});
+      conv(q + ".ffn.0", {x, li, f});
+      conv(q + ".ffn.1", {f, li, bo, 0, NO_VIEW, 0, x});
+      b = bo;
+    }
+    const VIn vin{View{pa, 2 * c, 0}, 0, b, c};
+    conv(p + ".cv2", {View{pa, 2 * c, 0}, li, out, 0, NO_VIEW, 0, NO_VIEW, &vin});
+  }
 };
+
+// YOLO11, segment A: model.0 (YOLOv8's k3 s2 conv on the u8 letterbox),
+// model.1, model.2
+static int seg_stem_v11(Exec& E, const uint8_t* lb) {
+  Model* M = E.M;
+  const Variant& v = M->def.v;
+  const View x0{M->X0, v.c1, 0}, x1{M->X1, v.c2, 0}, x2{M->X2, v.c3, 0};
+  const ConvSpec& c0 = M->def.convs[0];
+  const uint8_t* qb = M->dev + M->def.q_off;
+  const float* qs = (const float*)(qb + 3 * (size_t)c0.cout * 64);
+  const Conv0Q q0{(const int8_t*)qb, qs, qs + c0.cout, (const int32_t*)(qs + 2 * c0.cout)};
+  const double px0 = (double)E.B * M->map_h[1] * M->map_w[1];
+  // timed like the other families' stems: profile slot per_fwd - 1
+  E.status = M->prof.timed(M->prof.per_fwd - 1, E.s, 0, 2.0 * px0 * c0.cout * 27,
+                           (double)E.B * M->H * M->W * 3 + M->def.q_bytes + px0 * 2.0 * c0.cout, [&] {
+                             return launch_conv0(lb, E.B, M->H, M->W, q0, c0.cout,
+                                                 (bf16_t*)E.ptr(M->X0), v.c1, E.s);
+                           });
+  E.conv("model.1", {x0, 1, x1});
+  E.c3k2("model.2", {x1, 2, x2}, M->C2, v.c3 / 4, v.nb, v.c3k);
+  return E.status;
+}
+
+// YOLO11, segment B: model.3 .. model.16 (the rest of the backbone, SPPF,
+// C2PSA and the top-down neck).  The yaml's Upsample + Concat pairs (11-12,
+// 14-15) are virtual concat inputs of model.13.cv1 / model.16.cv1.
+static int seg_backbone_v11(Exec& E) {
+  Model* M = E.M;
+  const Variant& v = M->def.v;
+  const int sc = v.c5 / 2;
+  const View x2{M->X2, v.c3, 0}, x3{M->X3, v.c3, 0}, p3{M->X4, v.c4, 0}, x5{M->X5, v.c4, 0},
+      p4{M->X6, v.c4, 0}, x7{M->X7, v.c5, 0}, x8{M->X8, v.c5, 0}, sp{M->SP, 4 * sc, 0},
+      x9{M->X9, v.c5, 0};
+  // model.10 / model.13 as the bottom-up concats 21 / 18 hold them
+  const View t10{M->CAT20, E.cat20, v.h18}, t13{M->CAT17, E.cat17, v.h15};
+  const VIn vin13{t10, 1, p4, v.c5}, vin16{t13, 1, p3, v.h12};
+  E.conv("model.3", {x2, 2, x3});
+  E.c3k2("model.4", {x3, 3, p3}, M->C4, v.c4 / 4, v.nb, v.c3k);
+  E.conv("model.5", {p3, 3, x5});
+  E.c3k2("model.6", {x5, 4, p4}, M->C6, v.c4 / 2, v.nb, true);
+  E.conv("model.7", {p4, 4, x7});
+  E.c3k2("model.8", {x7, 5, x8}, M->C8, v.c5 / 2, v.nb, true);
+  E.conv("model.9.cv1", {x8, 5, sp});
+  if (!E.status)
+    E.status = launch_sppf_pool((bf16_t*)E.ptr(M->SP), E.B, M->map_h[5], M->map_w[5], sc, E.s);
+  E.conv("model.9.cv2", {sp, 5, x9});
+  E.c2psa("model.10", x9, 5, t10, v.nb);
+  E.c3k2("model.13", {t10, 4, t13, 0, NO_VIEW, 0, NO_VIEW, &vin13}, M->C12, v.h12 / 2, v.nb, v.c3k);
+  E.c3k2("model.16", {t13, 3, View{M->X15, v.h15, 0}, 0, NO_VIEW, 0, NO_VIEW, &vin16}, M->C15,
+         v.h15 / 2, v.nb, v.c3k);
+  return E.status;
+}
 
 // YOLOv5u, segment A: model.0 (k6 s2 p2 from the u8 letterbox, its own
 // kernel: Exec::out_dim's pad = k / 2 does not hold for it), model.1, model.2
@@ -708,7 +950,9 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
   // its fixed form (bf16 plan, 64-wide box branch, 80 or <= 64 classes, no
   // raw output / logits copy) and a candidate list is asked for; auto picks
   // it for pipeline-sized batches at a conf where candidates are sparse.
-  const bool fixed_head = fuse_head && !E.f8 && !raw_out && cand && v.c2d == 64 &&
+  // YOLO11 heads are dense only (their class branch is not the two 3x3 convs)
+  const bool v11 = v.family == kFamilyV11;
+  const bool fixed_head = fuse_head && !E.f8 && !v11 && !raw_out && cand && v.c2d == 64 &&
                           (v.nc == 80 || v.nc <= 64) && v.c3p == (v.nc == 80 ? 80 : 64);
   const bool sparse =
       fixed_head && (M->head_sparse == 1 ||
@@ -720,14 +964,25 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
                       c = M->def.head + "cv3." + std::to_string(i);
     const View da{M->DA[i], dcs, 0}, fb{M->DB[i], dcs, 0}, fc{M->DB[i], dcs, v.c2d},
         lg{M->HD[i], hcs, 0};
-    E.conv_pair(a + ".0", P[i], c + ".0", P[i], 3 + i, da);
-    if (sparse) {
+    if (v11) {
+      // class branch: DWConv 3x3 -> Conv 1x1, twice, beside the box branch's 3x3s
+      const std::string l = std::to_string(i);
+      const View wa{M->buf_of("DW" + l + "a"), P[i].cs, 0}, wb{M->buf_of("DW" + l + "b"), v.c3p, 0};
+      E.conv(a + ".0", {P[i], 3 + i, da});
+      E.dw(c + ".0.0", P[i], 0, 0, 3 + i, wa);
+      E.conv(c + ".0.1", {wa, 3 + i, View{M->DA[i], dcs, v.c2d}});
+      E.conv(a + ".1", {da, 3 + i, fb});
+      E.dw(c + ".1.0", View{M->DA[i], dcs, v.c2d}, 0, 0, 3 + i, wb);
+      E.conv(c + ".1.1", {wb, 3 + i, fc});
+    } else if (sparse) {
+      E.conv_pair(a + ".0", P[i], c + ".0", P[i], 3 + i, da);
       const ConvSpec* p1 = E.spec(a + ".1");
       if (!p1) return E.status;
       E.conv_in_sparse(a + ".1", {da, 3 + i, fb});
       E.conv(c + ".1", {View{M->DA[i], dcs, v.c2d}, 3 + i, fc});
       hbx[i] = HeadBoxLevel{(const bf16_t*)E.ptr(M->DA[i]), dcs, E.wptr(*p1), E.bptr(*p1)};
     } else {
+      E.conv_pair(a + ".0", P[i], c + ".0", P[i], 3 + i, da);
       E.conv_pair(a + ".1", da, c + ".1", View{M->DA[i], dcs, v.c2d}, 3 + i, fb);
     }
     HeadLevel& L = hl[i];
@@ -771,17 +1026,21 @@ static int seg_heads(Exec& E, float* raw_out, float conf, void* cand, int cand_c
   };
   // the bottom-up neck: a stride-2 conv into the level's concat, then its
   // block (YOLOv8: model.16, C2f 18, model.19, C2f 21; YOLOv5u: model.18,
-  // C3 20, model.21, C3 23)
+  // C3 20, model.21, C3 23; YOLO11: model.17, C3k2 19, model.20, C3k2 22)
   const bool v5 = v.family == kFamilyV5u;
   if (E.status || forked_head(0)) return E.status;
-  E.conv(v5 ? "model.18" : "model.16", {P[0], 3, c17});
-  if (v5)
+  E.conv(v11 ? "model.17" : (v5 ? "model.18" : "model.16"), {P[0], 3, c17});
+  if (v11)
+    E.c3k2("model.19", {c17, 4, P[1]}, M->C18, v.h18 / 2, v.nb, v.c3k);
+  else if (v5)
     E.c3("model.20", {c17, 4, P[1]}, M->C18, v.h18, v.nb, false);
   else
     E.c2f("model.18", {c17, 4, P[1]}, M->C18, v.h18, v.nb, false);
   if (E.status || forked_head(1)) return E.status;
-  E.conv(v5 ? "model.21" : "model.19", {P[1], 4, c20});
-  if (v5)
+  E.conv(v11 ? "model.20" : (v5 ? "model.21" : "model.19"), {P[1], 4, c20});
+  if (v11)
+    E.c3k2("model.22", {c20, 5, P[2]}, M->C21, v.h21 / 2, v.nb, true);
+  else if (v5)
     E.c3("model.23", {c20, 5, P[2]}, M->C21, v.h21, v.nb, false);
   else
     E.c2f("model.21", {c20, 5, P[2]}, M->C21, v.h21, v.nb, false);
@@ -958,7 +1217,8 @@ extern "C" int rv_yolo_forward(void* h, const uint8_t* lb, int B, void* ws, size
 }
 
 // part 0: the whole forward (segments A-C).  part 1: A-B, stem .. model.15
-// (YOLOv5u: .. model.17; its segments end at the same places of the graph)
+// (YOLOv5u: .. model.17, YOLO11: .. model.16; their segments end at the same
+// places of the graph)
 // (the backbone and the top-down neck: the bandwidth-heavy P2/P3 layers).
 // part 2: C, the rest (the bottom-up neck, the Detect heads and the decode:
 // small latency-bound launches), reading part 1's activations from the same
@@ -981,14 +1241,16 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
   RV_CHECK_ARG(M->scales_set, "fp8 plan: activation scales not set (rv_yolo_set_act_scales)");
   Exec E(M, ws, B, stream, std::move(off), raw_out != nullptr);
   M->trace.clear();
+  M->attn_trace.clear();
   M->launches.clear();
   M->fused.clear();
   M->li_base = part == 2 ? M->after_neck.n : (part == 4 ? M->after_stem.n : 0);
   static const int SEGS[5] = {7, 3, 4, 1, 2};  // per part: bit 0 = segment A, 1 = B, 2 = C
   const int segs = SEGS[part];
   auto here = [&] { return Resume{M->li_base + (int)M->launches.size(), B, ws}; };
-  const bool v5 = M->def.v.family == kFamilyV5u;
-  if ((segs & 1) && (v5 ? seg_stem_v5u(E, lb) : seg_stem(E, lb))) return E.status;
+  const bool v5 = M->def.v.family == kFamilyV5u, v11 = M->def.v.family == kFamilyV11;
+  if ((segs & 1) && (v11 ? seg_stem_v11(E, lb) : v5 ? seg_stem_v5u(E, lb) : seg_stem(E, lb)))
+    return E.status;
   if (part == 3) {
     M->after_stem = here();
     // part 3 rewrote the start of the workspace: a part 2 now needs the part 4
@@ -996,7 +1258,7 @@ extern "C" int rv_yolo_forward_part(void* h, const uint8_t* lb, int B, void* ws,
     M->after_neck = Resume{};
   }
   if (segs & 2) {
-    if (v5 ? seg_backbone_v5u(E) : seg_backbone(E)) return E.status;
+    if (v11 ? seg_backbone_v11(E) : v5 ? seg_backbone_v5u(E) : seg_backbone(E)) return E.status;
     M->after_neck = here();
   }
   return (segs & 4) ? seg_heads(E, raw_out, conf, cand, cand_cap, cand_n) : RV_OK;
@@ -1027,5 +1289,19 @@ extern "C" int rv_yolo_trace(void* h, int* recs, int max_recs) {
   static_assert(sizeof(TraceRec) == 24 * sizeof(int), "rv_yolo_trace: 24 ints per record");
   if (recs)
     for (int i = 0; i < n && i < max_recs; ++i) memcpy(recs + 24 * i, &M->trace[i], 24 * sizeof(int));
+  return n;
+}
+
+// One AttnRec (9 ints: qkv view {buf, cs, co}, heads, H, W, output view {buf,
+// cs, co}) per attention launch of the last forward (YOLO11's PSA blocks, in
+// launch order); returns the record count
+extern "C" int rv_yolo_attn_trace(void* h, int* recs, int max_recs) {
+  if (!h) return RV_EINVAL;
+  Model* M = (Model*)h;
+  const int n = (int)M->attn_trace.size();
+  static_assert(sizeof(AttnRec) == 9 * sizeof(int), "rv_yolo_attn_trace: 9 ints per record");
+  if (recs)
+    for (int i = 0; i < n && i < max_recs; ++i)
+      memcpy(recs + 9 * i, &M->attn_trace[i], 9 * sizeof(int));
   return n;
 }

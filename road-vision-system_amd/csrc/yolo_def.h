@@ -1,4 +1,4 @@
-// YOLOv8 / YOLOv5u model definition (yolo_def.hip): the canonical conv list
+// YOLOv8 / YOLOv5u / YOLO11 model definition (yolo_def.hip): the canonical conv list
 // of a variant (Ultralytics state_dict order, BN already fused into conv
 // weight + bias) and the layout of its packed weight blob.  Host code only.
 #pragma once
@@ -19,6 +19,10 @@ struct ConvSpec {
   // packed rows / columns beyond cout / cin are zero, so the extra channels
   // are exact zeros and every logical channel keeps its sums.
   int pcin = 0, pcout = 0;
+  // 1: dense; cin (= cout): depthwise (YOLO11's DWConv), state_dict weight
+  // [cout][1][k][k], packed for dwconv.hip as bf16 [k * k][pcout] (tap-major,
+  // zero beyond cout) instead of the dense layout
+  int groups = 1;
 };
 
 struct Variant {
@@ -26,7 +30,9 @@ struct Variant {
   int h12, h15, h18, h21;   // head widths
   int nb, nm;               // C2f repeats for "3" and "6"
   int nx = 0;               // YOLOv5u: C3 repeats for "9" (model.6)
-  int family = 0;           // kFamilyV8 (C2f graph, yolov8.yaml) / kFamilyV5u (C3 graph, yolov5.yaml)
+  int family = 0;           // kFamilyV8 (C2f graph, yolov8.yaml) / kFamilyV5u (C3 graph, yolov5.yaml) /
+                            // kFamilyV11 (C3k2 + C2PSA graph, yolo11.yaml)
+  bool c3k = false;         // YOLO11 m, l, x: every C3k2 nests C3k blocks
   int c2d, c3d;             // Detect branch widths (the Ultralytics ones)
   int nc = 80, reg = 16;
   int c3p;                  // c3d as the plan runs it: padded to a multiple of 8
@@ -37,9 +43,17 @@ struct Variant {
 // anchor-free re-release of YOLOv5: yolov5.yaml's C3 graph under the YOLOv8
 // Detect head).  For YOLOv5u h15 / h18 / h21 are the Detect inputs' widths
 // (model.17 / 20 / 23: c3, c4, c5) and h12 is model.14's (c3).
-constexpr int kFamilyV8 = 0, kFamilyV5u = 1;
-constexpr int kNumVariants = 10;
-inline int family_of(int variant) { return variant >= 5 ? kFamilyV5u : kFamilyV8; }
+// Variants 20..24: YOLO11 n, s, m, l, x (yolo11.yaml); 10..19 are no variant.
+// There h12 / h15 / h18 / h21 are the widths of model.13 / 16 / 19 / 22 (c4,
+// c3, c4, c5), nb is the repeat count of every C3k2 and of C2PSA.
+constexpr int kFamilyV8 = 0, kFamilyV5u = 1, kFamilyV11 = 2;
+constexpr int kV11Base = 20;
+inline bool variant_known(int variant) {
+  return (variant >= 0 && variant < 10) || (variant >= kV11Base && variant < kV11Base + 5);
+}
+inline int family_of(int variant) {
+  return variant >= kV11Base ? kFamilyV11 : (variant >= 5 ? kFamilyV5u : kFamilyV8);
+}
 
 // class counts a plan supports: the NMS class mask is 4 x 32 bits wide
 constexpr int kMinClasses = 1, kMaxClasses = 128;
@@ -86,6 +100,51 @@ struct ModelDef {
       add(p + ".m." + std::to_string(i) + ".cv2", c, c, 3, 1);
     }
   }
+  // YOLO11 C3k2(c1, c2, n, c3k, e): a C2f (cv1, cv2 on [y0 | y1 | m.i ...])
+  // whose m.i is Bottleneck(c, c) with hidden width c / 2 (3x3, 3x3), or with
+  // c3k a C3k(c, c): cv1, cv2 (c -> c / 2, 1x1), cv3 (c -> c, 1x1), two
+  // bottlenecks (3x3, 3x3) at width c / 2 -- the state_dict order
+  void c3k2(const std::string& p, int c1, int c2, int n, bool c3k, int e4 = 2) {
+    const int c = c2 * e4 / 4, h = c / 2;  // e = e4 / 4: 0.5 or 0.25
+    add(p + ".cv1", c1, 2 * c, 1, 1);
+    add(p + ".cv2", (2 + n) * c, c2, 1, 1);
+    for (int i = 0; i < n; ++i) {
+      const std::string q = p + ".m." + std::to_string(i);
+      if (!c3k) {
+        add(q + ".cv1", c, h, 3, 1);
+        add(q + ".cv2", h, c, 3, 1);
+        continue;
+      }
+      add(q + ".cv1", c, h, 1, 1);
+      add(q + ".cv2", c, h, 1, 1);
+      add(q + ".cv3", 2 * h, c, 1, 1);
+      for (int j = 0; j < 2; ++j) {
+        add(q + ".m." + std::to_string(j) + ".cv1", h, h, 3, 1);
+        add(q + ".m." + std::to_string(j) + ".cv2", h, h, 3, 1);
+      }
+    }
+  }
+  int add_dw(const std::string& n, int c, int act) {  // DWConv(c, c, 3)
+    const int i = add(n, c, c, 3, 1, act);
+    convs[i].groups = c;
+    return i;
+  }
+  // YOLO11 C2PSA(C, C, n): cv1 (C -> 2c, c = C / 2, split a | b), n PSA
+  // blocks on b (attn.qkv c -> 2c, attn.proj c -> c, attn.pe depthwise 3x3,
+  // all without activation; ffn.0 c -> 2c SiLU, ffn.1 2c -> c none), cv2
+  void c2psa(const std::string& p, int C, int n) {
+    const int c = C / 2;
+    add(p + ".cv1", C, 2 * c, 1, 1);
+    add(p + ".cv2", 2 * c, C, 1, 1);
+    for (int i = 0; i < n; ++i) {
+      const std::string q = p + ".m." + std::to_string(i);
+      add(q + ".attn.qkv", c, 2 * c, 1, 1, 0);
+      add(q + ".attn.proj", c, c, 1, 1, 0);
+      add_dw(q + ".attn.pe", c, 0);
+      add(q + ".ffn.0", c, 2 * c, 1, 1);
+      add(q + ".ffn.1", 2 * c, c, 1, 1, 0);
+    }
+  }
   int find(const std::string& n) const {
     for (size_t i = 0; i < convs.size(); ++i)
       if (convs[i].name == n) return (int)i;
@@ -96,7 +155,8 @@ struct ModelDef {
 // false: unknown variant / dtype, or nc outside [kMinClasses, kMaxClasses]
 bool build_def(int variant, ModelDef& m, int dtype = RV_YOLO_DTYPE_BF16, int nc = 80);
 // RV_OK, or RV_EINVAL with rv_last_error naming what is wrong with
-// (variant, dtype, nc): the range of nc, fp8 with nc != 80 or a YOLOv5u variant
+// (variant, dtype, nc): the range of nc, fp8 with nc != 80 or a YOLOv5u /
+// YOLO11 variant
 int check_plan_args(int variant, int dtype, int nc);
 size_t packed_bytes(const ModelDef& m);
 size_t flat_floats(const ModelDef& m);

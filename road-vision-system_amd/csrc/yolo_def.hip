@@ -1,7 +1,9 @@
-// YOLOv8 / YOLOv5u model definition + weight packer (restating the
-// Ultralytics yolov8.yaml graph: Conv / C2f / SPPF / Detect(DFL), and the
+// YOLOv8 / YOLOv5u / YOLO11 model definition + weight packer (restating the
+// Ultralytics yolov8.yaml graph: Conv / C2f / SPPF / Detect(DFL), the
 // yolov5.yaml graph of the "u" models: Conv k6 / C3 / SPPF under the same
-// Detect) and the C ABI entries that need no handle.  Host code only.
+// Detect, and the yolo11.yaml graph: C3k2 / C2PSA and a Detect whose class
+// branch is depthwise-separable) and the C ABI entries that need no handle.
+// Host code only.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,8 +21,32 @@ static bool variant_widths(int variant, Variant& v) {
   // yolov5.yaml scales (variants 5..9): depth, width, max channels 1024
   static const double S5[5][3] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 1024},
                                   {1.00, 1.00, 1024}, {1.33, 1.25, 1024}};
-  if (variant < 0 || variant >= kNumVariants) return false;
+  // yolo11.yaml scales (variants 20..24): depth, width, max channels
+  static const double S11[5][3] = {{0.50, 0.25, 1024}, {0.50, 0.50, 1024}, {0.50, 1.00, 512},
+                                   {1.00, 1.00, 512},  {1.00, 1.50, 512}};
+  if (!variant_known(variant)) return false;
   v.family = family_of(variant);
+  if (v.family == kFamilyV11) {
+    const int sc = variant - kV11Base;
+    const double d = S11[sc][0], w = S11[sc][1], mc = S11[sc][2];
+    auto ch = [&](int c) { return make_div8(std::min((double)c, mc) * w); };
+    v.c1 = ch(64);
+    v.c2 = ch(128);
+    v.c3 = ch(256);
+    v.c4 = ch(512);
+    v.c5 = ch(1024);
+    v.h12 = v.c4;  // model.13
+    v.h15 = v.c3;  // model.16 -> Detect P3
+    v.h18 = v.c4;  // model.19 -> Detect P4
+    v.h21 = v.c5;  // model.22 -> Detect P5
+    v.nb = v.nm = std::max((int)std::lround(2 * d), 1);
+    v.c3k = sc >= 2;
+    v.c2d = std::max(std::max(16, v.h15 / 4), v.reg * 4);
+    v.c3d = std::max(v.h15, std::min(v.nc, 100));
+    v.c3p = (v.c3d + 7) & ~7;
+    v.hcs = (4 * v.reg + v.nc + 3) & ~3;
+    return true;
+  }
   if (v.family == kFamilyV5u) {
     const double d = S5[variant - 5][0], w = S5[variant - 5][1], mc = S5[variant - 5][2];
     auto ch = [&](int c) { return make_div8(std::min((double)c, mc) * w); };
@@ -68,7 +94,7 @@ static size_t conv0q_bytes(int C0) { return 3 * (size_t)C0 * 64 + 20 * (size_t)C
 static size_t conv0q6_bytes(int C0) { return 9 * (size_t)C0 * 64 + 20 * (size_t)C0; }
 
 int check_plan_args(int variant, int dtype, int nc) {
-  RV_CHECK_ARG(variant >= 0 && variant < kNumVariants, "unknown variant %d", variant);
+  RV_CHECK_ARG(variant_known(variant), "unknown variant %d", variant);
   RV_CHECK_ARG(dtype == RV_YOLO_DTYPE_BF16 || dtype == RV_YOLO_DTYPE_FP8, "unknown dtype %d", dtype);
   RV_CHECK_ARG(nc >= kMinClasses && nc <= kMaxClasses, "nc = %d outside the supported range %d..%d",
                nc, kMinClasses, kMaxClasses);
@@ -77,6 +103,8 @@ int check_plan_args(int variant, int dtype, int nc) {
                "calibration; use the bf16 plan", nc);
   RV_CHECK_ARG(dtype != RV_YOLO_DTYPE_FP8 || family_of(variant) != kFamilyV5u,
                "YOLOv5u plans (variant %d) are bf16 only: there is no fp8 YOLOv5u plan", variant);
+  RV_CHECK_ARG(dtype != RV_YOLO_DTYPE_FP8 || family_of(variant) != kFamilyV11,
+               "YOLO11 plans (variant %d) are bf16 only: there is no fp8 YOLO11 plan", variant);
   return RV_OK;
 }
 
@@ -127,6 +155,51 @@ static void build_v5u(ModelDef& m) {
   add_detect(m, {v.h15, v.h18, v.h21});
 }
 
+// yolo11.yaml: layer numbers as in the yaml; Upsample (11, 14) and Concat
+// (12, 15, 18, 21) hold no weights.  The Detect class branch is
+// DWConv 3x3 -> Conv 1x1, twice, then the plain 1x1 (the box branch is
+// YOLOv8's); state_dict order: all of cv2, then all of cv3.
+static void build_v11(ModelDef& m) {
+  const Variant& v = m.v;
+  m.head = "model.23.";
+  m.add("model.0", 3, v.c1, 3, 2);
+  m.add("model.1", v.c1, v.c2, 3, 2);
+  m.c3k2("model.2", v.c2, v.c3, v.nb, v.c3k, 1);
+  m.add("model.3", v.c3, v.c3, 3, 2);
+  m.c3k2("model.4", v.c3, v.c4, v.nb, v.c3k, 1);
+  m.add("model.5", v.c4, v.c4, 3, 2);
+  m.c3k2("model.6", v.c4, v.c4, v.nb, true);
+  m.add("model.7", v.c4, v.c5, 3, 2);
+  m.c3k2("model.8", v.c5, v.c5, v.nb, true);
+  m.add("model.9.cv1", v.c5, v.c5 / 2, 1, 1);
+  m.add("model.9.cv2", v.c5 / 2 * 4, v.c5, 1, 1);
+  m.c2psa("model.10", v.c5, v.nb);
+  m.c3k2("model.13", v.c5 + v.c4, v.h12, v.nb, v.c3k);
+  m.c3k2("model.16", v.h12 + v.c4, v.h15, v.nb, v.c3k);
+  m.add("model.17", v.h15, v.h15, 3, 2);
+  m.c3k2("model.19", v.h15 + v.h12, v.h18, v.nb, v.c3k);
+  m.add("model.20", v.h18, v.h18, 3, 2);
+  m.c3k2("model.22", v.h18 + v.c5, v.h21, v.nb, true);
+  const int chs[3] = {v.h15, v.h18, v.h21};
+  for (int i = 0; i < 3; ++i) {
+    const std::string p = m.head + "cv2." + std::to_string(i);
+    m.add(p + ".0", chs[i], v.c2d, 3, 1);
+    m.add(p + ".1", v.c2d, v.c2d, 3, 1);
+    m.add(p + ".2", v.c2d, 4 * v.reg, 1, 1, 0);
+  }
+  for (int i = 0; i < 3; ++i) {
+    const std::string p = m.head + "cv3." + std::to_string(i);
+    // as in add_detect: the plan runs the branch c3p wide behind its first 1x1
+    m.add_dw(p + ".0.0", chs[i], 1);
+    m.convs[m.add(p + ".0.1", chs[i], v.c3d, 1, 1)].pcout = v.c3p;
+    ConvSpec& d1 = m.convs[m.add_dw(p + ".1.0", v.c3d, 1)];
+    d1.pcin = d1.pcout = v.c3p;
+    ConvSpec& c1 = m.convs[m.add(p + ".1.1", v.c3d, v.c3d, 1, 1)];
+    c1.pcin = c1.pcout = v.c3p;
+    m.convs[m.add(p + ".2", v.c3d, v.nc, 1, 1, 0)].pcin = v.c3p;
+  }
+}
+
 // yolov8.yaml
 static void build_v8(ModelDef& m) {
   const Variant& v = m.v;
@@ -155,15 +228,18 @@ bool build_def(int variant, ModelDef& m, int dtype, int nc) {
   m.v.nc = nc;
   if (!variant_widths(variant, m.v)) return false;
   if (dtype != RV_YOLO_DTYPE_BF16 && dtype != RV_YOLO_DTYPE_FP8) return false;
-  if (dtype == RV_YOLO_DTYPE_FP8 && m.v.family == kFamilyV5u) return false;
+  if (dtype == RV_YOLO_DTYPE_FP8 && m.v.family != kFamilyV8) return false;
   m.dtype = dtype;
   const Variant& v = m.v;
-  if (v.family == kFamilyV5u)
+  if (v.family == kFamilyV11)
+    build_v11(m);
+  else if (v.family == kFamilyV5u)
     build_v5u(m);
   else
     build_v8(m);
   // packed layout: conv 0 keeps f32 OIHW (VALU conv), the rest bf16
   // [Cout_pad16][ky][kx][Cin_pad32]; biases f32 [Cout_pad16]; 256-B aligned.
+  // Depthwise convs (YOLO11): bf16 [ky * 3 + kx][pcout], bias as the others.
   // fp8 plans: every conv but conv 0 and the Detect head's last 1x1 stage
   // (run inside the decode kernel on bf16 features) is fp8 e4m3
   // [Cout_pad16][ky][kx][Cin_pad64] + f32 per-cout scales [Cout_pad16].
@@ -178,7 +254,8 @@ bool build_def(int variant, ModelDef& m, int dtype, int nc) {
     const int cip = c.f8 ? (c.cin + 63) & ~63 : (c.cin + 31) & ~31;
     c.w_off = off;
     off = al(off + (i == 0 ? (size_t)c.cout * c.cin * c.k * c.k * 4
-                           : (size_t)cop * c.k * c.k * cip * (c.f8 ? 1 : 2)));
+                    : c.groups > 1 ? (size_t)c.k * c.k * c.pcout * 2
+                                   : (size_t)cop * c.k * c.k * cip * (c.f8 ? 1 : 2)));
     c.b_off = off;
     off = al(off + (size_t)cop * 4);
     if (c.f8) {
@@ -278,7 +355,7 @@ static void pack_conv0q6(const float* w, const float* b, int C0, uint8_t* dst) {
 
 size_t flat_floats(const ModelDef& m) {
   size_t n = 0;
-  for (const ConvSpec& c : m.convs) n += (size_t)c.cout * c.cin * c.k * c.k + c.cout;
+  for (const ConvSpec& c : m.convs) n += (size_t)c.cout * (c.cin / c.groups) * c.k * c.k + c.cout;
   return n;
 }
 
@@ -350,6 +427,14 @@ extern "C" int rv_yolo_conv_info_nc(int variant, int nc, int idx, int* info, cha
   return RV_OK;
 }
 
+extern "C" int rv_yolo_conv_groups(int variant, int nc, int idx) {
+  if (const int st = check_plan_args(variant, RV_YOLO_DTYPE_BF16, nc)) return st;
+  ModelDef m;
+  RV_CHECK_ARG(build_def(variant, m, RV_YOLO_DTYPE_BF16, nc), "unknown variant %d", variant);
+  RV_CHECK_ARG(idx >= 0 && idx < (int)m.convs.size(), "bad conv index %d", idx);
+  return m.convs[idx].groups;
+}
+
 extern "C" size_t rv_yolo_flat_floats(int variant) { return rv_yolo_flat_floats_nc(variant, 80); }
 
 extern "C" size_t rv_yolo_flat_floats_nc(int variant, int nc) {
@@ -402,7 +487,7 @@ extern "C" int rv_yolo_pack3(int variant, int dtype, int nc, const float* flat, 
   const float* p = flat;
   for (size_t i = 0; i < m.convs.size(); ++i) {
     const ConvSpec& c = m.convs[i];
-    const size_t nw = (size_t)c.cout * c.cin * c.k * c.k;
+    const size_t nw = (size_t)c.cout * (c.cin / c.groups) * c.k * c.k;
     const float* w = p;
     const float* b = p + nw;
     p += nw + c.cout;
@@ -412,6 +497,10 @@ extern "C" int rv_yolo_pack3(int variant, int dtype, int nc, const float* flat, 
         pack_conv0q6(w, b, c.cout, out + m.q_off);
       else
         pack_conv0q(w, b, c.cout, out + m.q_off);
+    } else if (c.groups > 1) {
+      uint16_t* dst = (uint16_t*)(out + c.w_off);
+      for (int o = 0; o < c.cout; ++o)
+        for (int t = 0; t < c.k * c.k; ++t) dst[(size_t)t * c.pcout + o] = host_f2bf(w[o * c.k * c.k + t]);
     } else if (c.f8) {
       // per output channel: scale = 2^ceil(log2(amax / 448)), codes RNE
       const int cip = (c.cin + 63) & ~63;

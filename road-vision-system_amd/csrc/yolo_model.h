@@ -35,6 +35,12 @@ struct TraceRec {  // 24 ints: rv_yolo_trace copies them out as they lie
   int split;
 };
 
+struct AttnRec {  // 9 ints: rv_yolo_attn_trace copies them out as they lie
+  View qkv;       // the qkv map: head h in channels co + 128 h + [0, 128)
+  int heads, H, W;
+  View out;       // o: head h in channels co + 64 h + [0, 64)
+};
+
 // A 1x1 conv's virtual concat input (ConvArgs::in2 / split / in_up):
 // channels [0, split) from view a (read upsampled 2x when up), the rest
 // from view b.
@@ -101,6 +107,7 @@ struct Model {
   ModelDef def;
   Profile prof;
   std::vector<TraceRec> trace;  // conv specs run by the last forward (one record each)
+  std::vector<AttnRec> attn_trace;  // attention launches of the last forward (YOLO11)
   std::vector<ConvArgs> launches;  // conv kernel launches of the last forward
   std::vector<ConvCfg> tuned;      // per launch index: autotuned config (mr 0 = default)
   struct FusedC2f {
@@ -169,7 +176,10 @@ struct Model {
   // YOLOv5u plans: the outputs of model.4 / 6 / 9 / 13 (P3, P4, SPPF and the
   // top-down P4 block), which no concat buffer holds there; CAT14 and CAT11
   // are -1 (both Upsample + Concat pairs are virtual), CAT17 / CAT20 are the
-  // yaml's concats 19 / 22 and X15 / X18 / X21 the Detect inputs 17 / 20 / 23
+  // yaml's concats 19 / 22 and X15 / X18 / X21 the Detect inputs 17 / 20 / 23.
+  // YOLO11 plans: X4 / X6 / X9 likewise (model.4 / 6 / 9), X13 unused (model.13
+  // lives in CAT17); CAT17 / CAT20 are the yaml's concats 18 / 21 and X15 / X18
+  // / X21 the Detect inputs 16 / 19 / 22 (yolo.hip plan_v11 names the rest)
   int X4 = -1, X6 = -1, X9 = -1, X13 = -1;
   int DA[3], DB[3], HD[3];
 

@@ -138,6 +138,13 @@ _SIGS = {
     "rv_conv_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                              c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                              c_void_p]),
+    "rv_yolo_conv_groups": (c_int, [c_int, c_int, c_int]),
+    "rv_dwconv3x3_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                  c_int, c_int, c_void_p]),
+    "rv_psa_attention_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                      c_int, c_void_p]),
+    "rv_yolo_attn_trace": (c_int, [c_void_p, c_void_p, c_int]),
     "rv_yolo_packed_bytes2": (c_size_t, [c_int, c_int]),
     "rv_yolo_pack2": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t]),
     "rv_yolo_create2": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, POINTER(c_void_p)]),
@@ -263,7 +270,7 @@ _RECORDABLE = {"rv_clahe_median_letterbox_u8", "rv_clahe_median_u8", "rv_letterb
 _NOCHECK = {"rv_preprocess_chain_route", "rv_sched_num_nodes", "rv_sched_event_query", "rv_abi_version", "rv_cand_segments", "rv_yolo_cand_segments", "rv_clahe_median_fits", "rv_clahe_median_letterbox_fits", "rv_yolo_num_convs", "rv_yolo_num_anchors",
             "rv_yolo_num_buffers", "rv_yolo_trace", "rv_yolo_profile_read", "rv_yolo_tuned_config",
             "rv_yolo_profile_bytes", "rv_yolo_profile_times", "rv_yolo_buffer_esize", "rv_yolo_conv_candidates",
-            "rv_yolo_num_classes", "rv_yolo_head_form"}
+            "rv_yolo_num_classes", "rv_yolo_head_form", "rv_yolo_attn_trace"}
 
 
 _recorder = None  # a schedule.Schedule while one is being recorded

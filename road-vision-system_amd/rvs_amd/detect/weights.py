@@ -1,4 +1,4 @@
-"""YOLOv8 and YOLOv5u weights for the HIP detector.
+"""YOLOv8, YOLOv5u and YOLO11 weights for the HIP detector.
 
 The conv list (names, shapes, order) comes from the native plan in
 csrc/yolo_def.hip (rv_yolo_conv_info) -- Ultralytics state_dict order with BN
@@ -34,6 +34,13 @@ class count is read from ``model.24.cv3.0.2.weight``.  There is no shipped
 calibration and no fp8 plan for it: it needs a ``detect.weights`` file and
 runs in bf16.  An anchor-based checkpoint of the original yolov5 repository
 (``model.24.m.*`` / ``model.24.anchors``) is a different network and refused.
+
+YOLO11 (``yolo11n.pt`` ... ``yolo11x.pt``, yolo11.yaml: C3k2 / C2PSA, Detect
+at ``model.23``) is variants 20..24 (resolve_model; variant_of keeps to the two
+conv-only families).  Its depthwise convs (``DWConv``: the Detect class
+branch's ``cv3.i.j.0`` and the attention's ``attn.pe``) are Conv blocks with a
+``[C, 1, 3, 3]`` weight, fused or unfused like the others (conv_groups).  As
+for YOLOv5u there is no shipped calibration and no fp8 plan.
 """
 from __future__ import annotations
 
@@ -80,17 +87,40 @@ def variant_of(model_name: str) -> int:
                      "n/s/m/l/x -- yolov5n.pt / yolov5nu.pt ... -- only)")
 
 
+V11_VARIANTS = {"n": 20, "s": 21, "m": 22, "l": 23, "x": 24}  # YOLO11 (include/rvhip.h)
+_V11_NAME = re.compile(r"yolo11([nsmlx])(\.[a-z0-9]+)?$")
+
+
+def resolve_model(model_name: str) -> int:
+    """The plan variant of the reference's cfg['model']: 'yolo11n.pt' /
+    'yolo11n' / 'weights/YOLO11N.pt' -> 20 ... 'yolo11x.pt' -> 24; every other
+    name as variant_of (YOLOv8 0..4, YOLOv5u 5..9).  The YOLO11 task models
+    (yolo11n-seg.pt, -cls, -pose, -obb) and other families raise."""
+    m = _V11_NAME.match(os.path.basename(str(model_name)).lower())
+    if m:
+        return V11_VARIANTS[m.group(1)]
+    try:
+        return variant_of(model_name)
+    except ValueError as e:
+        raise ValueError(f"{e}; YOLO11 detection models are yolo11n.pt ... yolo11x.pt") from None
+
+
 def is_v5u(variant: int) -> bool:
-    return int(variant) >= 5
+    return 5 <= int(variant) < 10
+
+
+def is_v11(variant: int) -> bool:
+    return int(variant) >= 20
 
 
 def family_name(variant: int) -> str:
-    return "YOLOv5u" if is_v5u(variant) else "YOLOv8"
+    return "YOLO11" if is_v11(variant) else ("YOLOv5u" if is_v5u(variant) else "YOLOv8")
 
 
 def head_prefix(variant: int) -> str:
-    """State_dict prefix of the Detect module: layer 22 of yolov8.yaml, 24 of yolov5.yaml."""
-    return "model.24." if is_v5u(variant) else "model.22."
+    """State_dict prefix of the Detect module: layer 22 of yolov8.yaml, 24 of
+    yolov5.yaml, 23 of yolo11.yaml."""
+    return "model.23." if is_v11(variant) else ("model.24." if is_v5u(variant) else "model.22.")
 
 
 NC_MIN, NC_MAX = 1, 128  # class counts the native plan supports (include/rvhip.h)
@@ -116,6 +146,22 @@ def conv_list(variant: int, nc: int = 80) -> List[Tuple[str, int, int, int, int,
         _lib.check(lib.rv_yolo_conv_info_nc(variant, int(nc), i, info, name, 96),
                    "rv_yolo_conv_info_nc")
         out.append((name.value.decode(), info[0], info[1], info[2], info[3], info[4]))
+    return out
+
+
+def conv_groups(variant: int, nc: int = 80) -> List[int]:
+    """Per conv of conv_list(variant, nc): 1 for a dense conv, the channel
+    count for a depthwise one (its state_dict weight is [C, 1, k, k])."""
+    lib = _lib.load()
+    n = lib.rv_yolo_num_convs_nc(variant, int(nc))
+    if n < 0:
+        _lib.check(n, "rv_yolo_num_convs_nc")
+    out = []
+    for i in range(n):
+        g = lib.rv_yolo_conv_groups(variant, int(nc), i)
+        if g < 0:
+            _lib.check(g, "rv_yolo_conv_groups")
+        out.append(g)
     return out
 
 
@@ -168,6 +214,10 @@ def synthetic_weights(variant: int, seed: int = 0, nc: int = 80) -> np.ndarray:
         raise ValueError(f"no synthetic calibration for YOLOv5u (variant {variant}) in "
                          f"{os.path.basename(_CALIB)}: a YOLOv5u model needs a detect.weights "
                          "file (a local state_dict of the 'u' checkpoint)")
+    if is_v11(variant):
+        raise ValueError(f"no synthetic calibration for YOLO11 (variant {variant}) in "
+                         f"{os.path.basename(_CALIB)}: a YOLO11 model needs a detect.weights "
+                         "file (a local state_dict of the checkpoint)")
     if int(nc) != 80:
         raise ValueError(f"no synthetic calibration for nc = {nc} in {os.path.basename(_CALIB)} "
                          "(the shipped calibration is 80-class); a model with a custom class "
@@ -240,7 +290,8 @@ def nc_of_state_dict(tensors: Dict[str, np.ndarray], variant: int = None) -> int
     """The class count of an Ultralytics DetectionModel state_dict: the first
     dimension of model.22.cv3.0.2.weight (a plain nn.Conv2d, so the key is the
     same before and after model.fuse(), with or without the "model." nesting);
-    with a YOLOv5u `variant`, of model.24.cv3.0.2.weight."""
+    with a YOLOv5u `variant`, of model.24.cv3.0.2.weight, with a YOLO11 one of
+    model.23.cv3.0.2.weight."""
     t = _strip_prefix(tensors)
     key = cls_key(variant)
     if key not in t:
@@ -261,11 +312,14 @@ def check_family(t: Dict[str, np.ndarray], variant: int) -> None:
         raise ValueError("the state_dict is an anchor-based YOLOv5 checkpoint of the original "
                          "yolov5 repository (it has model.24.m.* / model.24.anchors): a different "
                          "network; the anchor-free 'u' checkpoint (yolov5nu.pt ...) is needed")
-    other = 0 if is_v5u(variant) else 5  # any variant of the other family
-    if cls_key(variant) not in t and cls_key(other) in t:
-        raise ValueError(f"the state_dict is a {family_name(other)} one (Detect at "
-                         f"{head_prefix(other)[:-1]}) but detect.model names a "
-                         f"{family_name(variant)} model (Detect at {head_prefix(variant)[:-1]})")
+    if cls_key(variant) in t:
+        return
+    for other in (0, 5, 20):  # any variant of each other family
+        if family_name(other) != family_name(variant) and cls_key(other) in t:
+            raise ValueError(f"the state_dict is a {family_name(other)} one (Detect at "
+                             f"{head_prefix(other)[:-1]}) but detect.model names a "
+                             f"{family_name(variant)} model (Detect at "
+                             f"{head_prefix(variant)[:-1]})")
 
 
 def _shaped(t: Dict[str, np.ndarray], key: str, shape, variant: int, nc: int) -> np.ndarray:
@@ -284,14 +338,15 @@ def flat_from_state_dict(tensors: Dict[str, np.ndarray], variant: int, nc: int =
     disagrees with it is an error.  return_nc: (flat, nc) instead of flat."""
     t = _strip_prefix(tensors)
     check_family(t, variant)
-    have = nc_of_state_dict(t, variant if is_v5u(variant) else None)
+    have = nc_of_state_dict(t, variant if is_v5u(variant) or is_v11(variant) else None)
     if nc is not None and int(nc) != have:
         raise ValueError(f"detect.nc = {int(nc)} but the checkpoint has {have} classes "
                          f"({cls_key(variant)} has {have} rows)")
     nc = have
     parts = []
-    for name, cin, cout, k, s, act in conv_list(variant, nc):
-        shape = (cout, cin, k, k)
+    groups = conv_groups(variant, nc)
+    for (name, cin, cout, k, s, act), g in zip(conv_list(variant, nc), groups):
+        shape = (cout, cin // g, k, k)
         if name + ".conv.weight" in t:  # Conv block (conv + bn + SiLU)
             w = _shaped(t, name + ".conv.weight", shape, variant, nc)
             if name + ".bn.running_var" in t:
@@ -330,9 +385,9 @@ def check_fp8_nc(dtype: str, nc: int) -> None:
 
 
 def check_fp8_variant(dtype: str, variant: int) -> None:
-    if dtype == "fp8" and is_v5u(variant):
-        raise ValueError(f"dtype 'fp8' is not available for YOLOv5u (variant {int(variant)}): "
-                         "its plans are bf16 only; set detect.dtype to bf16")
+    if dtype == "fp8" and (is_v5u(variant) or is_v11(variant)):
+        raise ValueError(f"dtype 'fp8' is not available for {family_name(variant)} (variant "
+                         f"{int(variant)}): its plans are bf16 only; set detect.dtype to bf16")
 
 
 def pack(variant: int, flat: np.ndarray, dtype: str = "bf16", nc: int = 80) -> np.ndarray:
@@ -371,6 +426,10 @@ def detector_weights(det_cfg: dict, variant: int) -> Tuple[np.ndarray, int]:
         raise ValueError(f"detect.model={det_cfg.get('model')!r} is a YOLOv5u model and there is "
                          "no shipped synthetic calibration for it: set detect.weights to a local "
                          "state_dict of the 'u' checkpoint")
+    if is_v11(variant):
+        raise ValueError(f"detect.model={det_cfg.get('model')!r} is a YOLO11 model and there is "
+                         "no shipped synthetic calibration for it: set detect.weights to a local "
+                         "state_dict of the checkpoint")
     if not w:
         warnings.warn(f"detect.model={det_cfg.get('model', 'yolov8n.pt')!r} but no detect.weights "
                       "file is configured: using seeded SYNTHETIC weights (set detect.weights to "

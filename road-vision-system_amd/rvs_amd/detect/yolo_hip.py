@@ -24,7 +24,7 @@ from .base import Detector
 from .types import Detection
 from .weights import (COCO80, DTYPES, NC_MAX, NC_MIN, check_fp8_nc, check_fp8_variant,
                       detector_weights,
-                      names_from_config, pack, variant_of)
+                      names_from_config, pack, resolve_model)
 
 CAND_BYTES = 32
 
@@ -422,7 +422,7 @@ class YOLOHip(Detector):
         self.device = torch.device("cuda:0" if device in ("auto", None, "cpu") else device)
         if not torch.cuda.is_available():
             raise RuntimeError("YOLOHip needs an MI355X (HIP device); there is no CPU fallback")
-        self.variant = variant_of(cfg.get("model", "yolov8n.pt"))
+        self.variant = resolve_model(cfg.get("model", "yolov8n.pt"))
         self.flat, self.nc = detector_weights(cfg, self.variant)
         self.conf = float(cfg.get("conf_thres", 0.25))
         self.iou = float(cfg.get("iou_thres", 0.7))

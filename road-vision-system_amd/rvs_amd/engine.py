@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from .config import load_config
 from .detect.types import Detection
-from .detect.weights import detector_weights, names_from_config, variant_of
+from .detect.weights import detector_weights, names_from_config, resolve_model
 from .detect.yolo_hip import YoloEngine
 from .geometry import GroundProjector, build_camera_projectors, build_projector
 from .handback import Record, handback
@@ -66,7 +66,7 @@ class RoadVisionEngine:
         # their `enabled` key is set (src/config.py defaults both to False)
         self.detect_enabled = bool(det_cfg.get("enabled", False))
         self.tracking_enabled = bool(trk_cfg.get("enabled", False))
-        self.variant = variant_of(det_cfg.get("model", "yolov8n.pt"))
+        self.variant = resolve_model(det_cfg.get("model", "yolov8n.pt"))
         self.detector = None
         # class count and names: the checkpoint's / the config's (detect.nc,
         # detect.names); caller-supplied flat weights carry detect.nc classes
