@@ -124,6 +124,33 @@ int rv_clahe_median_letterbox_fits(int H, int W, int tiles, int k, const int* ge
 int rv_gray_span_u8(const uint8_t* in, int B, int H, int W, int pitch,
                     int* ws, int* span_out, void* stream);
 
+/* Dark-channel-prior dehaze (He, Sun, Tang), the inverse of the fog model
+ * I = J t + A (1 - t) (no reference counterpart: the stronger dehaze the
+ * reference's plugin registry leaves room for).  Integer arithmetic end to
+ * end, every division a floor division, every window the square around the
+ * pixel clipped to the frame (N pixels):
+ *   d   = patch x patch minimum of min(B, G, R)
+ *   n   = max(1, H W / 1000); L = the largest level with count(d >= L) >= n;
+ *         M = {d >= L}, cnt = |M|; A_c = max(1, (2 sum_M I_c + cnt) / (2 cnt))
+ *   nd  = patch x patch minimum of min_c min(255, (510 I_c + A_c) / (2 A_c))
+ *   t0  = 255 - ((wq nd + 128) >> 8)
+ *   radius 0: t = t0.  Otherwise a guided filter of t0 by the gray g of
+ *   rv_gray_span_u8 over (2 radius + 1)^2: with the box sums N, Sg, Sp, Sgp,
+ *   Sgg of 1, g, t0, g t0, g g:
+ *         aq = ((N Sgp - Sg Sp) << 14) / (N Sgg - Sg^2 + eq N^2)
+ *         bq = ((Sp << 14) - aq Sg) / N;  SA, SB = the box sums of aq, bq
+ *         t  = clamp((SA g + SB + (N << 13)) / (N << 14), 0, 255)
+ *   tt  = max(t, tq); J_c = clamp(A_c + ((I_c - A_c) 510 + tt) / (2 tt), 0, 255)
+ * Normalised parameters: patch odd in 3..31; wq = omega in 1/256, 1..256;
+ * tq = t_min in 1/255, 1..255; radius 0..64; eq = eps 65025, 1..2^20.
+ * H * W <= 2^24 (the per-level channel sums are 32-bit).  in and out may not
+ * alias.  air_out (nullable): {A_b, A_g, A_r, L, cnt} per frame; t_out
+ * (nullable): the B x H x W plane of t.  ws: 16-byte aligned. */
+size_t rv_dcp_ws_bytes(int B, int H, int W, int radius);
+int rv_dcp_dehaze_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int pitch,
+                     int patch, int wq, int tq, int radius, int eq, void* ws,
+                     size_t ws_bytes, int32_t* air_out, uint8_t* t_out, void* stream);
+
 /* PreprocessPipeline.__call__ (src/preprocess/pipeline.py:32-45) of any
  * chain of the built-in ops, followed by the detector's LetterBox
  * (src/detect/yolo_ultralytics.py:28-35), as stream-ordered launches only:
@@ -140,15 +167,34 @@ int rv_gray_span_u8(const uint8_t* in, int B, int H, int W, int pitch,
  * max(2, tile_grid); median_derain.py:11-13: k odd in [3, 9]). */
 #define RV_CHAIN_CLAHE 0
 #define RV_CHAIN_MEDIAN 1
+#define RV_CHAIN_DCP 2
 #define RV_CHAIN_YCRCB 0
 #define RV_CHAIN_LAB 1
 #define RV_CHAIN_MAX_OPS 4
+/* One op in 24 bytes.  A DCP op (rv_dcp_dehaze_u8's normalised parameters)
+ * keeps {kind, tq, radius, patch} in the four ints and {wq, eq} in the bytes
+ * of `clip`; never fused with a neighbour, its chain runs op by op. */
 typedef struct rv_chain_op {
-  int32_t kind;  /* RV_CHAIN_CLAHE / RV_CHAIN_MEDIAN */
-  int32_t space; /* CLAHE: RV_CHAIN_YCRCB / RV_CHAIN_LAB */
-  int32_t tiles; /* CLAHE: grid, 2..64 */
-  int32_t k;     /* median: 3, 5, 7 or 9 */
-  double clip;   /* CLAHE: clipLimit */
+  int32_t kind; /* RV_CHAIN_CLAHE / RV_CHAIN_MEDIAN / RV_CHAIN_DCP */
+  union {
+    int32_t space; /* CLAHE: RV_CHAIN_YCRCB / RV_CHAIN_LAB */
+    int32_t tq;    /* DCP: 1..255 */
+  };
+  union {
+    int32_t tiles;  /* CLAHE: grid, 2..64 */
+    int32_t radius; /* DCP: 0..64 */
+  };
+  union {
+    int32_t k;     /* median: 3, 5, 7 or 9 */
+    int32_t patch; /* DCP: odd, 3..31 */
+  };
+  union {
+    double clip; /* CLAHE: clipLimit */
+    struct {
+      int32_t wq; /* DCP: 1..256 */
+      int32_t eq; /* DCP: 1..2^20 */
+    };
+  };
 } rv_chain_op;
 typedef struct rv_chain_desc {
   int32_t enabled; /* preprocess.enabled */
@@ -178,7 +224,8 @@ typedef struct rv_chain_desc {
 int rv_preprocess_chain_route(const rv_chain_desc* desc, int H, int W, const int* geo);
 /* Workspace bytes for B frames of H x W with `pitch` bytes per row: the gate's
  * 2*B ints + B flags, the largest op's LUTs, and one scratch batch
- * (B*H*pitch) when the chain runs as two or more passes.  0 for a bad
+ * (B*H*pitch) when the chain runs as two or more passes, and
+ * rv_dcp_ws_bytes of the largest radius when it holds a DCP op.  0 for a bad
  * descriptor or shape (and when nothing is needed). */
 size_t rv_preprocess_chain_ws_bytes(const rv_chain_desc* desc, int B, int H, int W, int pitch);
 /* in -> out (proc) and, when lb_out and geo are both given, the letterbox

@@ -15,6 +15,7 @@
 // workspace is B x tiles^2 x 256 u8 (16 KB per frame at 8x8).
 #include <cstring>
 #include <mutex>
+#include "dehaze.h"
 #include "lab.h"
 #include "lbgeo.h"
 
@@ -1411,16 +1412,17 @@ static_assert(sizeof(rv_chain_desc) == RV_CHAIN_DESC_BYTES, "rv_chain_desc layou
 
 namespace {
 
-enum PassKind { kPassClahe = 0, kPassMedian = 1, kPassClaheMedian = 2 };
+enum PassKind { kPassClahe = 0, kPassMedian = 1, kPassClaheMedian = 2, kPassDcp = 3 };
 
 struct ChainPass {
   int kind, space, tiles, k;
   double clip;
+  DcpParams dcp;  // kPassDcp only
 };
 
 // How a descriptor runs on an H x W frame: the passes (adjacent CLAHE(YCrCb)
 // + median fused where rv_clahe_median_u8 would), the route and the
-// workspace layout [gate ints | LUTs | scratch batch].
+// workspace layout [gate ints | LUTs | scratch batch | DCP workspace].
 struct ChainPlan {
   bool identity;  // disabled or empty chain: proc = raw
   bool gate, lab;
@@ -1428,6 +1430,7 @@ struct ChainPlan {
   ChainPass pass[RV_CHAIN_MAX_OPS];
   int route;
   int lut_tiles;  // largest CLAHE grid (0: no CLAHE)
+  int dcp_radius;  // largest refine radius of a DCP pass (-1: no DCP)
 };
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -1450,6 +1453,11 @@ int check_desc(const rv_chain_desc* d) {
     } else if (o.kind == RV_CHAIN_MEDIAN) {
       RV_CHECK_ARG(o.k == 3 || o.k == 5 || o.k == 7 || o.k == 9,
                    "chain op %d: median k=%d must be 3,5,7,9", i, o.k);
+    } else if (o.kind == RV_CHAIN_DCP) {
+      char what[32];
+      snprintf(what, sizeof(what), "chain op %d: DCP", i);
+      const int st = dcp_check(DcpParams{o.patch, o.wq, o.tq, o.radius, o.eq}, 0, 0, what);
+      if (st) return st;
     } else {
       RV_CHECK_ARG(false, "chain op %d: unknown kind %d", i, o.kind);
     }
@@ -1469,12 +1477,20 @@ void make_plan(const rv_chain_desc& d, int H, int W, const LbGeo* G, ChainPlan& 
   p.lab = false;
   p.n = 0;
   p.lut_tiles = 0;
+  p.dcp_radius = -1;
   p.route = RV_CHAIN_ROUTE_OPS;
   if (p.identity) return;
   for (int i = 0; i < d.n_ops;) {
     const rv_chain_op& o = d.ops[i];
     ChainPass& q = p.pass[p.n++];
-    q = ChainPass{o.kind == RV_CHAIN_CLAHE ? kPassClahe : kPassMedian, o.space, o.tiles, o.k, o.clip};
+    if (o.kind == RV_CHAIN_DCP) {  // a pass of its own: never fused with a neighbour
+      q = ChainPass{kPassDcp, 0, 0, 0, 0.0, DcpParams{o.patch, o.wq, o.tq, o.radius, o.eq}};
+      p.dcp_radius = max(p.dcp_radius, o.radius);
+      ++i;
+      continue;
+    }
+    q = ChainPass{o.kind == RV_CHAIN_CLAHE ? kPassClahe : kPassMedian, o.space, o.tiles, o.k, o.clip,
+                  DcpParams{}};
     if (o.kind == RV_CHAIN_CLAHE) {
       p.lut_tiles = max(p.lut_tiles, o.tiles);
       p.lab = p.lab || o.space == RV_CHAIN_LAB;
@@ -1496,22 +1512,27 @@ void make_plan(const rv_chain_desc& d, int H, int W, const LbGeo* G, ChainPlan& 
 }
 
 struct ChainWs {
-  size_t gate, lut, scratch;  // byte sizes, in this order
-  size_t total() const { return gate + lut + scratch; }
+  size_t gate, lut, scratch, dcp;  // byte sizes, in this order
+  size_t total() const { return gate + lut + scratch + dcp; }
 };
 
-ChainWs plan_ws(const ChainPlan& p, int B, int H, int pitch) {
+ChainWs plan_ws(const ChainPlan& p, int B, int H, int W, int pitch) {
   ChainWs w;
   w.gate = p.gate ? align256((size_t)3 * B * sizeof(int)) : 0;
   w.lut = p.lut_tiles ? align256(lut_bytes(B, p.lut_tiles)) : 0;
   w.scratch = p.n >= 2 ? align256((size_t)B * H * pitch) : 0;
+  w.dcp = p.dcp_radius >= 0 && B > 0 ? align256(dcp_ws_bytes(B, H, W, p.dcp_radius)) : 0;
   return w;
 }
 
 // One pass src -> dst (flags: nullptr, or the gate's per-frame flags: frames
 // it passed through are skipped).
-void launch_pass(const ChainPass& q, const uint8_t* src, uint8_t* dst, uint8_t* lut, int B, int H,
-                 int W, int pitch, const int* flags, hipStream_t s) {
+void launch_pass(const ChainPass& q, const uint8_t* src, uint8_t* dst, uint8_t* lut, void* dcp_ws,
+                 int B, int H, int W, int pitch, const int* flags, hipStream_t s) {
+  if (q.kind == kPassDcp) {
+    launch_dcp(src, dst, B, H, W, pitch, q.dcp, dcp_ws, nullptr, nullptr, flags, s);
+    return;
+  }
   if (q.kind == kPassMedian) {
     const ClaheGeo g{};
     if (q.k != 3)
@@ -1561,7 +1582,8 @@ extern "C" size_t rv_preprocess_chain_ws_bytes(const rv_chain_desc* desc, int B,
   if (check_desc(desc) != RV_OK || B <= 0 || H <= 0 || W <= 0 || pitch < 3 * W) return 0;
   ChainPlan p;
   make_plan(*desc, H, W, nullptr, p);  // the layout does not depend on the letterbox
-  return plan_ws(p, B, H, pitch).total();
+  if (p.dcp_radius >= 0 && (int64_t)H * W > (1 << 24)) return 0;
+  return plan_ws(p, B, H, W, pitch).total();
 }
 
 extern "C" int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, int H, int W,
@@ -1581,7 +1603,10 @@ extern "C" int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, in
   if (geo != nullptr) RV_CHECK_ARG(lbgeo_from(geo, H, W, lb.g), "inconsistent letterbox geometry");
   ChainPlan p;
   make_plan(*desc, H, W, geo ? &lb.g : nullptr, p);
-  const ChainWs w = plan_ws(p, B, H, pitch);
+  if (p.dcp_radius >= 0)
+    RV_CHECK_ARG((int64_t)H * W <= (1 << 24) && B <= 65535,
+                 "a DCP op takes at most 65535 frames of 2^24 pixels (B=%d, %d x %d)", B, W, H);
+  const ChainWs w = plan_ws(p, B, H, W, pitch);
   RV_CHECK_ARG(w.total() == 0 || (ws != nullptr && ws_bytes >= w.total()),
                "workspace too small: %zu bytes, rv_preprocess_chain_ws_bytes says %zu", ws_bytes,
                w.total());
@@ -1633,7 +1658,7 @@ extern "C" int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, in
     const uint8_t* src = in;
     for (int i = 0; i < p.n; ++i) {
       uint8_t* dst = ((p.n - 1 - i) & 1) ? scratch : out;
-      launch_pass(p.pass[i], src, dst, lut, B, H, W, pitch, flags, s);
+      launch_pass(p.pass[i], src, dst, lut, scratch + w.scratch, B, H, W, pitch, flags, s);
       src = dst;
     }
     if (p.gate) launch_copy_frames(in, out, B, H, W, pitch, flags, s);

@@ -48,6 +48,10 @@ _SIGS = {
     "rv_clahe_median_letterbox_fits": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "rv_gray_span_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
+    "rv_dcp_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rv_dcp_dehaze_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                 c_void_p]),
     "rv_preprocess_chain_route": (c_int, [c_void_p, c_int, c_int, POINTER(c_int)]),
     "rv_preprocess_chain_ws_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "rv_preprocess_chain_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,

@@ -267,6 +267,37 @@ def clahe_median_fits(frames: torch.Tensor, tiles: int, k: int) -> bool:
     return bool(_lib.load().rv_clahe_median_fits(H, W, int(tiles), int(k)))
 
 
+def dcp_ws_bytes(B: int, H: int, W: int, radius: int) -> int:
+    """Workspace bytes of rv_dcp_dehaze_u8 (0 for a bad shape or radius)."""
+    return int(_lib.load().rv_dcp_ws_bytes(int(B), int(H), int(W), int(radius)))
+
+
+def dcp_dehaze(frames: torch.Tensor, patch: int = 15, wq: int = 243, tq: int = 26,
+               radius: int = 40, eq: int = 65, out: Optional[torch.Tensor] = None,
+               ws: Optional[torch.Tensor] = None, air: bool = False, t: bool = False):
+    """Dark-channel-prior dehaze (rv_dcp_dehaze_u8) of device frames with the
+    normalised parameters of preprocess.ops.dcp_params (the defaults are that
+    function's).  Returns the frames; with air and/or t also the (B, 5) int32
+    {A_b, A_g, A_r, L, cnt} and the (B, H, W) uint8 transmission, in that
+    order."""
+    x, B, H, W, pitch = _frames(frames)
+    out = _like(x, out)
+    need = dcp_ws_bytes(B, H, W, radius)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    air_t = torch.empty((B, 5), dtype=torch.int32, device=x.device) if air else None
+    t_t = torch.empty((B, H, W), dtype=torch.uint8, device=x.device) if t else None
+    call("rv_dcp_dehaze_u8", ptr(x), ptr(out), B, H, W, pitch, int(patch), int(wq), int(tq),
+         int(radius), int(eq), ptr(ws), ws.numel(), ptr(air_t), ptr(t_t), stream_ptr())
+    single = frames.dim() != 4
+    res = [out[0] if single else out]
+    if air:
+        res.append(air_t[0] if single else air_t)
+    if t:
+        res.append(t_t[0] if single else t_t)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 CHAIN_DESC_BYTES = 120  # sizeof(rv_chain_desc), include/rvhip.h
 CHAIN_MAX_OPS = 4
 ROUTE_FUSED, ROUTE_FUSED_GATED, ROUTE_OPS = 0, 1, 2  # RV_CHAIN_ROUTE_*
@@ -274,8 +305,9 @@ ROUTE_FUSED, ROUTE_FUSED_GATED, ROUTE_OPS = 0, 1, 2  # RV_CHAIN_ROUTE_*
 
 def chain_desc(ops, enabled: bool = True, gate_on: bool = False, contrast_thresh: float = 20.0):
     """The host descriptor (rv_chain_desc) of a preprocess chain.  ops: a list
-    of ("clahe", space, tiles, clip) and ("median", k) tuples holding the
-    normalised parameters (preprocess.ops.clahe_params / median_ksize).
+    of ("clahe", space, tiles, clip), ("median", k) and ("dcp", patch, wq, tq,
+    radius, eq) tuples holding the normalised parameters (preprocess.ops.
+    clahe_params / median_ksize / dcp_params).
     Nothing is validated here: the library checks the descriptor (n_ops,
     tiles, k, ...) and answers RV_EINVAL."""
     ops = list(ops)
@@ -288,8 +320,11 @@ def chain_desc(ops, enabled: bool = True, gate_on: bool = False, contrast_thresh
                                 float(clip))
         elif op[0] == "median":
             blob += struct.pack("<iiiid", 1, 0, 0, int(op[1]), 0.0)
+        elif op[0] == "dcp":
+            _, patch, wq, tq, radius, eq = op
+            blob += struct.pack("<iiiiii", 2, int(tq), int(radius), int(patch), int(wq), int(eq))
         else:
-            raise ValueError(f"chain op {op[0]!r}: expected 'clahe' or 'median'")
+            raise ValueError(f"chain op {op[0]!r}: expected 'clahe', 'median' or 'dcp'")
     assert len(blob) == CHAIN_DESC_BYTES
     return (ctypes.c_uint8 * CHAIN_DESC_BYTES).from_buffer_copy(blob)
 

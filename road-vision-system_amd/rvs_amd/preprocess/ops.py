@@ -31,6 +31,22 @@ def median_ksize(params):
     return k
 
 
+def dcp_params(params):
+    """(patch, wq, tq, radius, eq): DarkChannelDehaze's parameters as the
+    integers rv_dcp_dehaze_u8 takes.  patch odd in [3, 31]; omega in 1/256;
+    t_min in 1/255; refine_radius in [0, 64] (0: no refinement); eps (on
+    gray in [0, 1]) in 1/65025."""
+    p = int(params.get("patch", 15))
+    if p % 2 == 0:
+        p += 1
+    p = max(3, min(p, 31))
+    wq = min(256, max(1, int(float(params.get("omega", 0.95)) * 256 + 0.5)))
+    tq = min(255, max(1, int(float(params.get("t_min", 0.1)) * 255 + 0.5)))
+    r = min(64, max(0, int(params.get("refine_radius", 40))))
+    eq = min(1 << 20, max(1, int(float(params.get("eps", 1e-3)) * 65025 + 0.5)))
+    return p, wq, tq, r, eq
+
+
 def _to_device(image):
     """np.ndarray (H,W,3) u8 -> (device tensor, was_numpy)."""
     if isinstance(image, torch.Tensor):
@@ -77,9 +93,33 @@ class MedianDerain(PreprocessOp):
         return _back(kernels.median(x, self.k), was_np)
 
 
+class DarkChannelDehaze(PreprocessOp):
+    """Dark-channel-prior dehaze (He, Sun, Tang): the inverse of the fog model
+    I = J t + A (1 - t) that augment.fog synthesises, with a guided-filter
+    refinement of the transmission; integer arithmetic, HIP kernels
+    (csrc/dehaze.hip).  params: patch, omega, t_min, refine_radius, eps."""
+
+    def __init__(self, **params):
+        super().__init__(**params)
+        self.patch, self.wq, self.tq, self.radius, self.eq = dcp_params(self.params)
+        self._ws = None
+
+    def __call__(self, image):
+        x, was_np = _to_device(image)
+        B = 1 if x.dim() == 3 else x.shape[0]
+        need = kernels.dcp_ws_bytes(B, x.shape[-3], x.shape[-2], self.radius)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
+            self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+        out = kernels.dcp_dehaze(x, self.patch, self.wq, self.tq, self.radius, self.eq,
+                                 ws=self._ws)
+        return _back(out, was_np)
+
+
 # The reference registers its OpenCV-CUDA variants under these names
 # (src/preprocess/registry.py:19-23); on MI355X they are the same HIP ops.
 HIPCLAHEDehaze = CLAHEDehaze
 HIPMedianDerain = MedianDerain
 CUDACLAHEDehaze = CLAHEDehaze
 CUDAMedianDerain = MedianDerain
+DCPDehaze = DarkChannelDehaze
+HIPDarkChannelDehaze = DarkChannelDehaze

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from .. import kernels
-from .ops import CLAHEDehaze, MedianDerain, _back, _to_device
+from .ops import CLAHEDehaze, DarkChannelDehaze, MedianDerain, _back, _to_device
 from .registry import get_op_class
 
 
@@ -52,6 +52,8 @@ class PreprocessPipeline:
                 ops.append(("clahe", op.space, op.grid, op.clip_limit))
             elif type(op) is MedianDerain:
                 ops.append(("median", op.k))
+            elif type(op) is DarkChannelDehaze:
+                ops.append(("dcp", op.patch, op.wq, op.tq, op.radius, op.eq))
             else:
                 return None, str(node.get("name"))
         if len(ops) > kernels.CHAIN_MAX_OPS:

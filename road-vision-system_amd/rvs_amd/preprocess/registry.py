@@ -2,7 +2,7 @@
 from typing import Dict, Type
 
 from .base import PreprocessOp
-from .ops import CLAHEDehaze, MedianDerain
+from .ops import CLAHEDehaze, DarkChannelDehaze, MedianDerain
 
 REGISTRY: Dict[str, Type[PreprocessOp]] = {
     "CLAHEDehaze": CLAHEDehaze,
@@ -13,6 +13,10 @@ REGISTRY: Dict[str, Type[PreprocessOp]] = {
     "CUDAMedianDerain": MedianDerain,
     "HIPCLAHEDehaze": CLAHEDehaze,
     "HIPMedianDerain": MedianDerain,
+    # no reference counterpart: the stronger dehaze its registry leaves room for
+    "DarkChannelDehaze": DarkChannelDehaze,
+    "DCPDehaze": DarkChannelDehaze,
+    "HIPDarkChannelDehaze": DarkChannelDehaze,
 }
 
 

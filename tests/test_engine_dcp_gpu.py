@@ -1,0 +1,74 @@
+"""The chain [DarkChannelDehaze, MedianDerain] on the engine, in the manner of
+test_engine_chain_gpu.py: sequential step() calls give the reference's proc
+(tests/dcp_ref.py, then the oracle's median), and PipelinedRun(mode="native")
+replays the recorded chain twice with the same proc and the same detections."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+from dcp_ref import dcp_ref
+from oracle import cpu
+
+pytestmark = pytest.mark.gpu
+
+S, H, W, K = 3, 360, 640, 4
+IMG = [[560, 1000], [1360, 1000], [1160, 620], [760, 620]]
+WLD = [[-3.5, 5.0], [3.5, 5.0], [3.5, 30.0], [-3.5, 30.0]]
+
+
+def _cfg():
+    from rvs_amd.config import load_config
+    cfg = copy.deepcopy(load_config())
+    cfg["geometry"]["enabled"] = True
+    cfg["geometry"]["projector"]["image_points"] = IMG
+    cfg["geometry"]["projector"]["world_points"] = WLD
+    cfg["preprocess"]["chain"] = [{"name": "DarkChannelDehaze", "params": {}},
+                                  {"name": "MedianDerain", "params": {"ksize": 3}}]
+    return cfg
+
+
+def _key(res):
+    return [[(d.x1, d.y1, d.x2, d.y2, d.conf, d.cls_id, d.track_id, d.distance_m, d.speed_kmh)
+             for d in s] for s in res]
+
+
+def test_recorded_pipeline_runs_the_dcp_chain(cuda):
+    from rvs_amd.engine import RoadVisionEngine
+    from rvs_amd.preprocess.ops import dcp_params
+    from rvs_amd.schedule import PipelinedRun
+    from rvs_amd.synth import road_frames
+    cfg = _cfg()
+    frames = road_frames(S, K, H, W, device=cuda)
+    ts = [torch.full((S,), k / 30.0, dtype=torch.float64, device=cuda) for k in range(K)]
+    host = frames.cpu().numpy()
+    p = dcp_params({})
+    want_proc = [np.stack([cpu.median(dcp_ref(host[k, s], *p)[0], 3) for s in range(S)])
+                 for k in range(K)]
+
+    seq = RoadVisionEngine(cfg, S, (H, W), device=cuda)
+    assert not seq.fused_letterbox and seq.pipeline.chain_supported
+    seq_res, seq_proc = [], []
+    for r in range(2):
+        for k in range(K):
+            out = seq.step(frames[k], ts[k])
+            seq_res.append(_key(seq.results(out)))
+            seq_proc.append(out["proc"].cpu().numpy())
+    for k in range(K):
+        np.testing.assert_array_equal(seq_proc[k], want_proc[k], err_msg=f"step() proc {k}")
+
+    pip = RoadVisionEngine(cfg, S, (H, W), device=cuda, lanes=2, pair=2)
+    run = PipelinedRun(pip, [frames[k] for k in range(K)], ts, mode="native")
+    assert run.sched.num_nodes() > 0
+    for r in range(2):  # the second run replays the recorded descriptor
+        run.run()
+        torch.cuda.synchronize()
+        for k, o in enumerate(run.outs):
+            assert _key(pip.results(o)) == seq_res[r * K + k], f"run {r} step {k}"
+            np.testing.assert_array_equal(o["proc"].cpu().numpy(), want_proc[k],
+                                          err_msg=f"run {r} proc {k}")
+    np.testing.assert_array_equal(frames.cpu().numpy(), host)  # inputs untouched
+    run.close()
+    seq.close()
+    pip.close()
