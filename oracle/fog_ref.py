@@ -182,11 +182,12 @@ def gray_u8(img):
     return ((i[..., 0] * 1868 + i[..., 1] * 9617 + i[..., 2] * 4899 + 8192) >> 14).astype(np.uint8)
 
 
-def gaussian_kernel(k, sigma):
-    """getGaussianKernel(k, sigma > 0, CV_32F): computed in double, cast."""
+def gaussian_kernel(k, sigma, dtype=F):
+    """getGaussianKernel(k, sigma > 0, CV_32F): computed in double, cast
+    (dtype=np.float64 returns the values before the cast)."""
     x = np.arange(k, dtype=np.float64) - (k - 1) * 0.5
     t = np.exp((-0.5 / (sigma * sigma)) * x * x)
-    return (t * (1.0 / t.sum())).astype(F)
+    return (t * (1.0 / t.sum())).astype(dtype)
 
 
 def _sep_pass(img, kern, axis):
@@ -281,16 +282,24 @@ def add_weighted_u8(a, alpha, b, beta):
     return np.clip(np.rint(v), 0, 255).astype(np.uint8)
 
 
-def airlight_rgb(img_f):
-    """_airlight_from_image's sky colour before the tint (fog.py:120-127)."""
+def airlight_stages(img_f):
+    """_airlight_from_image's intermediates (fog.py:120-127): the band's f32
+    luminance, its 0.9-quantile, the mask count and the sky colour before
+    the tint."""
     h = img_f.shape[0]
     band_h = max(10, int(0.12 * h))
     top = img_f[:band_h]
     lum = 0.299 * top[:, :, 2] + 0.587 * top[:, :, 1] + 0.114 * top[:, :, 0]
     thr = np.quantile(lum, 0.9)
     mask = lum >= thr
-    a = top.mean(axis=(0, 1)) if mask.sum() < 100 else top[mask].mean(axis=0)
-    return a.astype(F)
+    count = int(mask.sum())
+    a = top.mean(axis=(0, 1)) if count < 100 else top[mask].mean(axis=0)
+    return dict(band_h=band_h, lum=lum, thr=thr, mask=mask, mask_count=count, a=a.astype(F))
+
+
+def airlight_rgb(img_f):
+    """_airlight_from_image's sky colour before the tint (fog.py:120-127)."""
+    return airlight_stages(img_f)["a"]
 
 
 def depth_and_sky(h, w, y_h_ratio=0.42, vx_ratio=0.5, sky_boost=1.25, road_damp=0.9,
@@ -312,12 +321,12 @@ def depth_and_sky(h, w, y_h_ratio=0.42, vx_ratio=0.5, sky_boost=1.25, road_damp=
     return np.clip(d * fac[:, None], F(0), F(1)).astype(F), sw.astype(F)
 
 
-def depth_bands(depth, beta, depth_blur_max):
-    """_depth_blur's per-band kernel sizes (fog.py:194-209): [(band mask,
-    rad)] for the bands that blur (rad > 1)."""
+def depth_bands_indexed(depth, beta, depth_blur_max):
+    """_depth_blur's per-band kernel sizes (fog.py:194-209): [(band index,
+    band mask, rad)] for the bands that blur (rad > 1)."""
     r = np.clip(depth * depth_blur_max * (0.5 + beta), 0.0, depth_blur_max * 1.5)
     out, prev = [], np.zeros_like(depth)
-    for b in (0.33, 0.66, 1.0):
+    for i, b in enumerate((0.33, 0.66, 1.0)):
         mask = ((depth >= prev) & (depth < b)).astype(F)
         prev = np.full_like(depth, b)
         if mask.sum() < 100:
@@ -325,26 +334,40 @@ def depth_bands(depth, beta, depth_blur_max):
         rad = int(max(1, np.mean(r[mask > 0]) * 1.5)) | 1
         if rad <= 1:
             continue
-        out.append((mask, rad))
+        out.append((i, mask, rad))
     return out
 
 
-def glow(img, strength):
-    """_glow (fog.py:182-192)."""
+def depth_bands(depth, beta, depth_blur_max):
+    """[(band mask, rad)] of depth_bands_indexed."""
+    return [(m, rad) for _, m, rad in depth_bands_indexed(depth, beta, depth_blur_max)]
+
+
+def glow(img, strength, stages=None):
+    """_glow (fog.py:182-192); `stages` (a dict) receives the threshold before
+    and after its clip, the hard mask's share and the two kernel sizes."""
     g = gray_u8((img * 255).astype(np.uint8)).astype(F) / 255.0
-    thr = np.clip(g.mean() + 0.6 * g.std(), 0.65, 0.9)
+    raw = g.mean() + 0.6 * g.std()
+    thr = np.clip(raw, 0.65, 0.9)
     hard = (g > thr).astype(F)
     k = int(9 + 20 * strength) | 1
     soft = np.clip(gaussian_blur(hard, k, k * 0.35), 0, 1)
     k2 = int(max(7, (img.shape[0] + img.shape[1]) * (0.003 + 0.01 * strength))) | 1
     blur = gaussian_blur(img, k2, k2 * 0.25)
+    if stages is not None:
+        stages.update(glow_thr_raw=float(raw), glow_thr=float(thr), glow_share=float(hard.mean()),
+                      glow_k=k, glow_k2=k2)
     return np.clip(img * (1 - soft[..., None]) + (img + strength * blur) * soft[..., None], 0, 1)
 
 
-def depth_blur(hazy, depth, strength, depth_blur_max):
-    """_depth_blur (fog.py:194-215)."""
+def depth_blur(hazy, depth, strength, depth_blur_max, stages=None):
+    """_depth_blur (fog.py:194-215); `stages` (a dict) receives the active
+    (band, rad) list."""
     out = hazy.copy()
-    for mask, rad in depth_bands(depth, strength, depth_blur_max):
+    active = depth_bands_indexed(depth, strength, depth_blur_max)
+    if stages is not None:
+        stages["bands"] = [(i, rad) for i, _, rad in active]
+    for _, mask, rad in active:
         blurred = gaussian_blur(hazy, rad, rad * 0.5)
         m3 = gaussian_blur(mask, rad | 1, rad * 0.5)[..., None]
         out = out * (1 - m3) + blurred * m3
@@ -388,20 +411,36 @@ def draw_full(rng, h, w, level="medium", mor=None, scale_ratio=0.18, n_oct=2, ra
                 cdrop=cdrop, tint=tint, gamma=gamma, noise=noise, rain_seed=int(seed))
 
 
-def fog_frame_full(img, prm, y_h_ratio=0.42, vx_ratio=0.5, sky_boost=1.25, road_damp=0.9,
-                   softness_ratio=0.06, global_veil=0.06, depth_blur_max=3.5,
-                   edge_guided=True, scale_ratio=0.18, n_oct=2, rain_p=0.0, rain_len=16):
+def fog_stages_full(img, prm, y_h_ratio=0.42, vx_ratio=0.5, sky_boost=1.25, road_damp=0.9,
+                    softness_ratio=0.06, global_veil=0.06, depth_blur_max=3.5,
+                    edge_guided=True, scale_ratio=0.18, n_oct=2, rain_p=0.0, rain_len=16):
     """EnhancedFogSynthesizer.synthesize (fog.py:227-299) with every filter,
-    on one (h, w, 3) u8 BGR frame and the draws of draw_full()."""
+    on one (h, w, 3) u8 BGR frame and the draws of draw_full(): a dict of the
+    intermediates a device stage can be held to, and the fogged frame `out`.
+      noise_min / noise_max   the raw value noise's range (f32)
+      lum, thr, mask_count    the airlight band's f32 luminance, its
+                              0.9-quantile, the count of lum >= thr
+      a_rgb_raw, a_rgb        the sky colour before / after tint and clip
+      amap_mean, amap_scale   the filtered airlight map's mean, a_target / it
+      t0, t                   transmission before / after the bilateral
+      glow_thr_raw, glow_thr, glow_share, glow_k, glow_k2
+      kernels                 {(k, sigma): getGaussianKernel f32} as used
+      bands                   the active (band, rad) list of the depth blur
+      fade_d                  the contrast fade's bilateral diameter"""
+    st = {}
     h, w = img.shape[:2]
     x = img.astype(F) / 255.0
     depth, sw = depth_and_sky(h, w, y_h_ratio, vx_ratio, sky_boost, road_damp, softness_ratio)
     octs, norm = octaves(h, w, scale_ratio, n_oct)
     nz = noise(h, w, prm["grids"], octs, norm)
+    st["noise_min"], st["noise_max"] = nz.min(), nz.max()
     nn = (nz - nz.min()) / max(F(1e-6), nz.max() - nz.min())
     beta_map = (prm["beta"] * (F(0.85) + F(0.35) * nn)).astype(F)
     # airlight (fog.py:120-139, 257-258)
-    a_rgb = np.clip(airlight_rgb(x) + prm["tint_a"], 0.7, 1.0)
+    air = airlight_stages(x)
+    st.update(lum=air["lum"], thr=air["thr"], mask_count=air["mask_count"], a_rgb_raw=air["a"])
+    a_rgb = np.clip(air["a"] + prm["tint_a"], 0.7, 1.0)
+    st["a_rgb"] = a_rgb
     vg = np.linspace(1.0, 0.85, h, dtype=F)[:, None, None]
     xg = np.linspace(0.95, 1.05, w, dtype=F)[None, :, None]
     amap = vg * a_rgb[None, None, :] * xg
@@ -409,17 +448,24 @@ def fog_frame_full(img, prm, y_h_ratio=0.42, vx_ratio=0.5, sky_boost=1.25, road_
         amap[:, :, c] = bilateral_f32(amap[:, :, c], 33, 12, 12)
     amap = np.clip(amap, 0.7, 1.0)
     scale = prm["a_target"] / max(1e-6, amap.mean())
+    st["amap_mean"], st["amap_scale"] = amap.mean(), scale
     amap = np.clip(amap * scale, 0.75, 1.0)
     # transmission (fog.py:172-179)
     t = np.clip(np.exp(-beta_map * depth), 0.05, 1.0)
+    st["t0"] = t
     if edge_guided:
         t = np.clip(bilateral_f32(t, 17, 12, 12), 0.05, 1.0)
+    st["t"] = t
     t3 = t[..., None]
     hazy = x * t3 + amap * (1.0 - t3)
     gv = (global_veil * (0.6 + 0.4 * sw))[:, None, None]
     hazy = np.clip(hazy * (1.0 - gv) + amap * gv, 0, 1)
-    hazy = glow(hazy, prm["glow"])
-    hazy = depth_blur(hazy, depth, prm["beta"], depth_blur_max)
+    hazy = glow(hazy, prm["glow"], st)
+    hazy = depth_blur(hazy, depth, prm["beta"], depth_blur_max, st)
+    st["fade_d"] = int(5 + prm["cdrop"] * 20) | 1
+    sizes = [(st["glow_k"], st["glow_k"] * 0.35), (st["glow_k2"], st["glow_k2"] * 0.25)]
+    sizes += [(rad, rad * 0.5) for _, rad in st["bands"]]
+    st["kernels"] = {ks: gaussian_kernel(*ks) for ks in sizes}
     hazy = contrast_fade(hazy, prm["cdrop"])
     hazy = np.clip(hazy * prm["tint"][None, None, :], 0, 1)
     if prm["gamma"] != 1.0:
@@ -435,4 +481,10 @@ def fog_frame_full(img, prm, y_h_ratio=0.42, vx_ratio=0.5, sky_boost=1.25, road_
                          _lowbias32(col * np.uint32(0x9E3779B1) + _lowbias32(seg)))
         rain = (hsh < thr)[..., None]
         hazy = np.where(rain, hazy + (F(1) - hazy) * F(0.45), hazy)
-    return (hazy * 255.0 + 0.5).astype(np.uint8)
+    st["out"] = (hazy * 255.0 + 0.5).astype(np.uint8)
+    return st
+
+
+def fog_frame_full(img, prm, **options):
+    """fog_stages_full's fogged frame (same options)."""
+    return fog_stages_full(img, prm, **options)["out"]
