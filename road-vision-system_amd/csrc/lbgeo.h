@@ -1,6 +1,6 @@
 // Ultralytics LetterBox geometry and the cv2.resize(INTER_LINEAR) 8U
 // per-axis coefficients, shared by the standalone letterbox kernel
-// (letterbox.hip) and the fused CLAHE+median+letterbox pass (preprocess.hip)
+// (letterbox.hip) and the fused CLAHE+median+letterbox pass (median.hip)
 // so both produce the same bytes.
 #pragma once
 #include <math.h>

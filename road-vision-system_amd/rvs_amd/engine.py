@@ -133,9 +133,6 @@ class RoadVisionEngine:
         # result hand-back: device staging buffer + the pinned host record of step()
         self.record = Record(self.S, self.max_det, self.device)
         self.rec_stage = torch.empty(self.record.nbytes, dtype=torch.uint8, device=self.device)
-        # default chain: CLAHE + median + the detector's LetterBox in one pass
-        self.fused_letterbox = self.detector is not None and \
-            self.pipeline.letterbox_fusable(self.H, self.W, self.detector.geo)
         # vis.draw (main_preview.py:113-116): the overlays of annotate() and of
         # a recording with preview.record.content "annotated" / "compare"
         draw_cfg = (cfg.get("vis") or {}).get("draw") or {}
@@ -231,50 +228,32 @@ class RoadVisionEngine:
             raise ValueError(f"{what} needs the detector (detect.enabled is false); "
                              "step() runs the preprocess-only path")
 
-    def preprocess_stage(self, frames: torch.Tensor, lb_slot: int = 0, lb_off: int = 0):
+    def preprocess_stage(self, frames: torch.Tensor, lb_slot: int = 0, lb_off: int = 0,
+                         proc: Optional[torch.Tensor] = None):
         """pipeline(raw) + the detector's LetterBox (main_preview.py:94-99)
         for (S,H,W,3) u8 device frames -> (proc, letterboxed batch in the
-        detector's letterbox slot `lb_slot`, images [lb_off, lb_off + S))."""
-        B = frames.shape[0]
-        if self.fused_letterbox:
-            return self.pipeline.run_with_letterbox(frames, self.detector.geo,
-                                                    self.detector.lb[lb_slot][lb_off:lb_off + B])
+        detector's letterbox slot `lb_slot`, images [lb_off, lb_off + S)).
+        proc: a caller-owned buffer to fill (rvs_amd.schedule: a recorded
+        schedule must not allocate per run)."""
         if self.pipeline.chain_supported:
-            # any other chain of the built-in ops, the gate included: one
+            # any chain of the built-in ops, the gate included: one
             # stream-ordered library call (the gate is evaluated on the device)
             if self.detector is None:
-                return self.pipeline.run_chain_with_letterbox(frames)
+                return self.pipeline.run_chain_with_letterbox(frames, out=proc)
+            B = frames.shape[0]
             return self.pipeline.run_chain_with_letterbox(
-                frames, self.detector.geo, self.detector.lb[lb_slot][lb_off:lb_off + B])
-        proc = self.pipeline(frames)
-        if self.detector is None:
-            return proc, None
-        return proc, self.detector.letterbox(proc, lb_slot, lb_off)
-
-    def preprocess_into(self, frames: torch.Tensor, proc: torch.Tensor, lb_slot: int = 0,
-                        lb_off: int = 0) -> None:
-        """preprocess_stage into a caller-owned proc buffer (rvs_amd.schedule:
-        a recorded schedule must not allocate per run)."""
-        B = frames.shape[0]
-        if self.fused_letterbox:
-            self.pipeline.run_with_letterbox(frames, self.detector.geo,
-                                             self.detector.lb[lb_slot][lb_off:lb_off + B], out=proc)
-            return
-        if self.pipeline.chain_supported:
-            if self.detector is None:
-                self.pipeline.run_chain_with_letterbox(frames, out=proc)
-            else:
-                self.pipeline.run_chain_with_letterbox(
-                    frames, self.detector.geo, self.detector.lb[lb_slot][lb_off:lb_off + B],
-                    out=proc)
-            return
-        if _lib._recorder is not None:
+                frames, self.detector.geo, self.detector.lb[lb_slot][lb_off:lb_off + B], out=proc)
+        if proc is not None and _lib._recorder is not None:
             raise RuntimeError("a recorded schedule needs a preprocess chain of the built-in ops "
                                "(CLAHEDehaze / MedianDerain, at most 4): this chain has "
                                f"{self.pipeline.unsupported_op}, which runs eagerly with torch "
                                "allocations and copies")
-        p, _ = self.preprocess_stage(frames, lb_slot, lb_off)
+        p = self.pipeline(frames)
+        lb = None if self.detector is None else self.detector.letterbox(p, lb_slot, lb_off)
+        if proc is None:
+            return p, lb
         proc.copy_(p)
+        return proc, lb
 
     def yolo_stage(self, lb: Optional[torch.Tensor], slot: int = 0, lane: int = 0,
                    part: int = 0, batch: Optional[int] = None) -> None:

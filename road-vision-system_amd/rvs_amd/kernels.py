@@ -44,18 +44,18 @@ def clahe_ws_bytes(B: int, tiles: int) -> int:
     return int(_lib.load().rv_clahe_ws_bytes(B, tiles))
 
 
-def _ws(B, tiles, ws, device):
-    need = clahe_ws_bytes(B, tiles)
+def _workspace(ws: Optional[torch.Tensor], need: int, device) -> torch.Tensor:
+    """ws if it holds `need` bytes, else a new buffer that does."""
     if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-    return ws, need
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    return ws
 
 
 def clahe_ycrcb(frames: torch.Tensor, tiles: int = 8, clip: float = 2.0,
                 out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
     x, B, H, W, pitch = _frames(frames)
     out = _like(x, out)
-    ws, need = _ws(B, tiles, ws, x.device)
+    ws = _workspace(ws, clahe_ws_bytes(B, tiles), x.device)
     call("rv_clahe_ycrcb_u8", ptr(x), ptr(out), B, H, W, pitch, int(tiles), float(clip),
          ptr(ws), ws.numel(), stream_ptr())
     return out if frames.dim() == 4 else out[0]
@@ -64,16 +64,22 @@ def clahe_ycrcb(frames: torch.Tensor, tiles: int = 8, clip: float = 2.0,
 _lab_ready = set()  # devices whose Lab tables are uploaded
 
 
+def _lab_tables(device) -> None:
+    """The Lab tables, uploaded once per device: synchronous, so it happens
+    before anything records."""
+    if device not in _lab_ready:
+        with torch.cuda.device(device):
+            call("rv_lab_init")
+        _lab_ready.add(device)
+
+
 def clahe_lab(frames: torch.Tensor, tiles: int = 8, clip: float = 2.0,
               out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
     """CLAHEDehaze space='LAB' (clahe_dehaze.py:21-25) on device frames."""
     x, B, H, W, pitch = _frames(frames)
     out = _like(x, out)
-    ws, need = _ws(B, tiles, ws, x.device)
-    if x.device not in _lab_ready:  # one synchronous upload per device, before capture
-        with torch.cuda.device(x.device):
-            call("rv_lab_init")
-        _lab_ready.add(x.device)
+    ws = _workspace(ws, clahe_ws_bytes(B, tiles), x.device)
+    _lab_tables(x.device)
     call("rv_clahe_lab_u8", ptr(x), ptr(out), B, H, W, pitch, int(tiles), float(clip),
          ptr(ws), ws.numel(), stream_ptr())
     return out if frames.dim() == 4 else out[0]
@@ -197,9 +203,7 @@ def jpeg_coef_to_stream(records: torch.Tensor, W: int, H: int, sampling, quality
     S = records.shape[0]
     rstride = records.stride(0) if S > 1 else records.shape[1] // 16 * 16
     out, stride, cap = _jpeg_streams(S, W, H, samp, capacity, out, records.device)
-    need = int(_lib.load().rv_jpeg_stream_ws_bytes(S, W, H, samp))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=records.device)
+    ws = _workspace(ws, int(_lib.load().rv_jpeg_stream_ws_bytes(S, W, H, samp)), records.device)
     fh = (1 if samp == 0 else 2) * 8
     hdr = jpeg_file_header(W, H, samp, quality, (W + fh - 1) // fh)
     call("rv_jpeg_coef_to_stream", ptr(records), rstride, S, int(W), int(H), samp, hdr, len(hdr),
@@ -217,9 +221,7 @@ def jpeg_encode(frames: torch.Tensor, quality: int = 95, sampling="420",
         x = x.contiguous()
     samp = jpeg_sampling_code(sampling)
     out, stride, cap = _jpeg_streams(S, W, H, samp, capacity, out, x.device)
-    need = int(_lib.load().rv_jpeg_encode_ws_bytes(S, W, H, samp))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws, int(_lib.load().rv_jpeg_encode_ws_bytes(S, W, H, samp)), x.device)
     call("rv_jpeg_encode_bgr_u8", ptr(x), S, H, W, samp, int(quality), ptr(ws), ws.numel(),
          ptr(out), stride, cap, stream_ptr())
     return out
@@ -236,7 +238,7 @@ def clahe_median(frames: torch.Tensor, tiles: int = 8, clip: float = 2.0, k: int
                  out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
     x, B, H, W, pitch = _frames(frames)
     out = _like(x, out)
-    ws, need = _ws(B, tiles, ws, x.device)
+    ws = _workspace(ws, clahe_ws_bytes(B, tiles), x.device)
     call("rv_clahe_median_u8", ptr(x), ptr(out), B, H, W, pitch, int(tiles), float(clip),
          int(k), ptr(ws), ws.numel(), stream_ptr())
     return out if frames.dim() == 4 else out[0]
@@ -251,7 +253,7 @@ def clahe_median_letterbox(frames: torch.Tensor, tiles: int, clip: float, k: int
     out = _like(x, out)
     if lb_out is None:
         lb_out = torch.empty((B, geo[0], geo[1], 3), dtype=torch.uint8, device=x.device)
-    ws, need = _ws(B, tiles, ws, x.device)
+    ws = _workspace(ws, clahe_ws_bytes(B, tiles), x.device)
     call("rv_clahe_median_letterbox_u8", ptr(x), ptr(out), B, H, W, pitch, int(tiles),
          float(clip), int(k), ptr(ws), ws.numel(), ptr(lb_out), _lib.int_array(geo), stream_ptr())
     return (out if frames.dim() == 4 else out[0]), lb_out
@@ -282,9 +284,7 @@ def dcp_dehaze(frames: torch.Tensor, patch: int = 15, wq: int = 243, tq: int = 2
     order."""
     x, B, H, W, pitch = _frames(frames)
     out = _like(x, out)
-    need = dcp_ws_bytes(B, H, W, radius)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws, dcp_ws_bytes(B, H, W, radius), x.device)
     air_t = torch.empty((B, 5), dtype=torch.int32, device=x.device) if air else None
     t_t = torch.empty((B, H, W), dtype=torch.uint8, device=x.device) if t else None
     call("rv_dcp_dehaze_u8", ptr(x), ptr(out), B, H, W, pitch, int(patch), int(wq), int(tq),
@@ -378,13 +378,9 @@ def preprocess_chain(frames: torch.Tensor, desc, geo=None, out: Optional[torch.T
             raise ValueError("lb_out needs the letterbox geometry (geo)")
     elif lb_out is None:
         lb_out = torch.empty((B, geo[0], geo[1], 3), dtype=torch.uint8, device=x.device)
-    need = preprocess_chain_ws_bytes(desc, B, H, W, pitch)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
-    if _desc_has_lab(desc) and x.device not in _lab_ready:
-        with torch.cuda.device(x.device):  # one synchronous upload per device, never recorded
-            call("rv_lab_init")
-        _lab_ready.add(x.device)
+    ws = _workspace(ws, preprocess_chain_ws_bytes(desc, B, H, W, pitch), x.device)
+    if _desc_has_lab(desc):
+        _lab_tables(x.device)
     call("rv_preprocess_chain_u8", ptr(x), ptr(out), B, H, W, pitch, desc, ptr(ws), ws.numel(),
          ptr(lb_out), None if geo is None else _lib.int_array(geo), stream_ptr())
     return proc, lb_out

@@ -1,7 +1,7 @@
 """HIP preprocess ops (drop-in for src/preprocess/ops/*.py and ops_cuda/*.py).
 
 ``CLAHEDehaze`` restates clahe_dehaze.py:13-32 and ``MedianDerain`` restates
-median_derain.py:10-14 on the gfx950 kernels of csrc/preprocess.hip.  Parameter
+median_derain.py:10-14 on the gfx950 kernels of csrc/clahe.hip and median.hip.  Parameter
 parsing follows the reference line by line (grid clamp, ksize normalisation).
 """
 from __future__ import annotations

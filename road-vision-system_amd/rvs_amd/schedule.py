@@ -286,7 +286,7 @@ class PipelinedRun:
         slot = u % eng.detector.slots
         for h in range(self.units[u]):
             k = self.k0[u] + h
-            eng.preprocess_into(self.frames[k], self.procs[k], slot, h * S)
+            eng.preprocess_stage(self.frames[k], slot, h * S, proc=self.procs[k])
 
     def _y1(self, u: int, E: "_Events" = None, stream=None) -> None:
         eng = self.eng

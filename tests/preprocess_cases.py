@@ -3,7 +3,7 @@ test_preprocess_paths_gpu.py): every case is one call of one entry of
 csrc/preprocess.hip on named frames, with the oracle's answer (oracle.cpu,
 computed once per process and shared, read-only) and, from the host side
 alone, the kernel path the call takes (path_of: the path predicates of
-preprocess.hip restated in Python, each citing the line it mirrors; the CPU
+the library restated in Python, each citing the function it mirrors; the CPU
 test holds them to the library's own host queries) and the regime the data
 is in (clahe_stats, unclamped_crcb, unsaturated_bgr, split_share: numpy on
 the oracle's planes).  test_preprocess_cases_cpu.py asserts paths and
@@ -137,10 +137,10 @@ def frames_of(case):
 
 
 # ---------------------------------------------------------------------------
-# the path predicates of csrc/preprocess.hip, restated
+# the path predicates of csrc/{clahe,median,preprocess}.hip, restated
 # ---------------------------------------------------------------------------
-kBW, kBH, kLutWinMax = 128, 16, 48                 # preprocess.hip:388-389
-kM3W, kM3H, kM3TW, kM3TH, kCellMax = 128, 32, 136, 34, 16   # preprocess.hip:603-607
+kBW, kBH, kLutWinMax = 128, 16, 48                 # median.hip: median_tile_kernel
+kM3W, kM3H, kM3TW, kM3TH, kCellMax = 128, 32, 136, 34, 16   # median.hip: med3_kernel
 
 
 class Geo(NamedTuple):
@@ -151,7 +151,7 @@ class Geo(NamedTuple):
 
 
 def make_geo(H, W, tiles, clip=0.0):
-    """preprocess.hip:52 make_geo."""
+    """clahe.h: make_geo."""
     if W % tiles == 0 and H % tiles == 0:
         tw, th = W // tiles, H // tiles
     else:
@@ -161,25 +161,25 @@ def make_geo(H, W, tiles, clip=0.0):
 
 
 def clahe_packed_ok(g):
-    """preprocess.hip:274 clahe_packed_ok."""
+    """clahe.hip: clahe_packed_ok."""
     per_thread = 4 * (((g.tw // 4) * g.th + 255) // 256) + (g.tw * g.th + 255) // 256
     return 8 * per_thread <= 65535
 
 
 def med3_cells(g):
-    """preprocess.hip:1046 med3_cells."""
+    """median.hip: med3_cells."""
     ncx = min((kM3TW + g.tw - 1) // g.tw + 2, g.tiles + 1)
     ncy = min((kM3TH + g.th - 1) // g.th + 2, g.tiles + 1)
     return ncx * ncy
 
 
 def med3_cells_fit(g):
-    """preprocess.hip:1052 med3_cells_fit."""
+    """median.hip: med3_cells_fit."""
     return med3_cells(g) <= kCellMax
 
 
 def lut_window_fits(g, K):
-    """preprocess.hip:1202 lut_window_fits."""
+    """median.hip: lut_window_fits."""
     R = K // 2
     cols = (kBW + 2 * R - 1) // g.tw + 3
     rows = (kBH + 2 * R - 1) // g.th + 3
@@ -187,13 +187,13 @@ def lut_window_fits(g, K):
 
 
 def clahe_median_fits(H, W, tiles, k):
-    """preprocess.hip:1354 rv_clahe_median_fits."""
+    """median.hip: clahe_median_fuses (rv_clahe_median_fits)."""
     g = make_geo(H, W, tiles)
     return (k == 3 and med3_cells_fit(g)) or lut_window_fits(g, k)
 
 
 def lut_loader(H, W, g, pitch, base):
-    """preprocess.hip:121-123, the LUT loader's `inside` and `vec`, over the
+    """clahe.hip: clahe_lut_body, the LUT loader's `inside` and `vec`, over the
     whole grid: 'vec' when every tile loads dwords, 'mixed' when only the
     tiles inside the frame do, else 'scalar'.  (A frame's base is in + b H
     pitch and a tile's x0 = tx tw: both keep the alignment when pitch % 4 ==
@@ -206,7 +206,7 @@ def lut_loader(H, W, g, pitch, base):
 
 
 def dword_io(pitch, *bases):
-    """preprocess.hip:1077 (launch_med3: in and out) and :1196 (launch_gray_span: in)."""
+    """median.hip: launch_med3_as (in and out); preprocess.hip: launch_gray_span (in)."""
     return "vec" if pitch % 4 == 0 and all(b % 4 == 0 for b in bases) else "scalar"
 
 
@@ -215,7 +215,7 @@ def _f32(v):
 
 
 def lb_taps(n_dst, scale, n, vertical):
-    """lbgeo.h:31 lb_tap_x / :56 lb_tap_y for every destination index:
+    """lbgeo.h: lb_tap_x / lb_tap_y for every destination index:
     (s0, s1) after the zero-weight redirection, and w1."""
     d = np.arange(n_dst, dtype=np.float64)
     f = _f32((d + 0.5) * scale - 0.5)
@@ -237,13 +237,13 @@ def lb_taps(n_dst, scale, n, vertical):
 
 
 def lbgeo_ok(geo):
-    """lbgeo.h:78 lbgeo_from's consistency test."""
+    """lbgeo.h: lbgeo_from's consistency test."""
     oh, ow, nh, nw, top, left = geo
     return nh > 0 and nw > 0 and top >= 0 and left >= 0 and top + nh <= oh and left + nw <= ow
 
 
 def med3_lb_fits(geo, H, W):
-    """preprocess.hip:1059 med3_lb_fits."""
+    """median.hip: med3_lb_fits."""
     _, _, nh, nw, _, _ = geo
     if nw > W or nh > H:
         return False
@@ -253,20 +253,20 @@ def med3_lb_fits(geo, H, W):
 
 
 def lb_is_copy(geo, H, W):
-    """preprocess.hip:658 lb_is_copy."""
+    """median.hip: lb_is_copy."""
     _, _, nh, nw, _, _ = geo
     return bool((lb_taps(nw, 1.0 / (nw / W), W, False)[2] == 0).all() and
                 (lb_taps(nh, 1.0 / (nh / H), H, True)[2] == 0).all())
 
 
 def letterbox_fits(H, W, tiles, k, geo):
-    """preprocess.hip:1361 rv_clahe_median_letterbox_fits."""
+    """preprocess.hip: rv_clahe_median_letterbox_fits."""
     return k == 3 and lbgeo_ok(geo) and med3_cells_fit(make_geo(H, W, tiles)) and \
         med3_lb_fits(geo, H, W)
 
 
 def chain_passes(ops, H, W):
-    """preprocess.hip:1466 make_plan, the passes: ('clahe', space, tiles,
+    """preprocess.hip: make_plan, the passes: ('clahe', space, tiles,
     clip), ('median', k) or ('clahe_median', tiles, clip, k)."""
     out, i = [], 0
     while i < len(ops):
@@ -282,7 +282,7 @@ def chain_passes(ops, H, W):
 
 
 def chain_route(ops, enabled, gate, H, W, geo=None):
-    """preprocess.hip:1466 make_plan, the route."""
+    """preprocess.hip: make_plan, the route."""
     if not enabled or not ops:
         return ROUTE_OPS
     p = chain_passes(ops, H, W)

@@ -2,7 +2,8 @@
 PipelinedRun(mode="native") of an engine whose chain is not the fused default
 (ksize 5, LAB, the low-contrast gate, preprocess off, a one-op chain) against
 sequential step() calls of a second engine and against the oracle's chain;
-a chain holding a custom op still needs mode="eager"."""
+a chain holding a custom op still needs mode="eager".  The default chain
+takes the same entry: its bytes against the fused per-op entry's."""
 import copy
 
 import numpy as np
@@ -73,6 +74,7 @@ def _key(res):
 
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_recorded_pipeline_runs_any_builtin_chain(cuda, inputs, name):
+    from rvs_amd import kernels
     from rvs_amd.engine import RoadVisionEngine
     from rvs_amd.schedule import PipelinedRun
     edit, ref, gate = CONFIGS[name]
@@ -88,7 +90,11 @@ def test_recorded_pipeline_runs_any_builtin_chain(cuda, inputs, name):
                            for s in range(S)]) for k in range(K)]
 
     seq = RoadVisionEngine(cfg, S, (H, W), device=cuda)
-    assert not seq.fused_letterbox and seq.pipeline.chain_supported
+    assert seq.pipeline.chain_supported
+    # none of them is the plain fused default: op by op, except the default
+    # chain behind the gate, which has a fused route of its own
+    assert seq.pipeline.chain_route(H, W, seq.detector.geo) == \
+        (kernels.ROUTE_FUSED_GATED if gate else kernels.ROUTE_OPS)
     seq_res, seq_proc = [], []
     for r in range(2):
         for k in range(K):
@@ -114,6 +120,47 @@ def test_recorded_pipeline_runs_any_builtin_chain(cuda, inputs, name):
     run.close()
     seq.close()
     pip.close()
+
+
+# (H, W) -> the default chain's route with the detector's 640 letterbox.
+# 1024 x 1024 is the smallest size of preprocess_cases that takes ROUTE_FUSED
+# there; 1080p is the benchmark's geometry, whose med3 grid (15 x 34 tiles per
+# frame) is no multiple of 8 at B = 3; 37 x 91 upscales, so it runs op by op.
+DEFAULT_CHAIN_SIZES = [(1024, 1024, "ROUTE_FUSED"), (1080, 1920, "ROUTE_FUSED"),
+                       (37, 91, "ROUTE_OPS")]
+
+
+@pytest.mark.parametrize("h,w,route", DEFAULT_CHAIN_SIZES)
+def test_default_chain_through_the_chain_entry_equals_the_fused_entry(cuda, h, w, route):
+    """The engine has one way into the library, rv_preprocess_chain_u8, for
+    the default chain too: its proc and letterboxed batch equal, byte for
+    byte, what rv_clahe_median_letterbox_u8 gives where the chain's route is
+    ROUTE_FUSED, and rv_clahe_median_u8 + rv_letterbox_u8 where it is not."""
+    from rvs_amd import kernels
+    from rvs_amd.engine import RoadVisionEngine
+    from rvs_amd.synth import road_frames
+    eng = RoadVisionEngine(_cfg(), S, (h, w), device=cuda)
+    geo = eng.detector.geo
+    assert eng.pipeline.chain_supported and not eng.pipeline._gate_enabled()
+    assert eng.pipeline.chain_route(h, w, geo) == getattr(kernels, route)  # a host query
+    frames = road_frames(S, 1, h, w, device=cuda)[0]
+    host = frames.cpu().numpy()
+    if route == "ROUTE_FUSED":
+        want_proc, want_lb = kernels.clahe_median_letterbox(frames, 8, 2.0, 3, geo)
+    else:
+        want_proc = kernels.clahe_median(frames, 8, 2.0, 3)
+        want_lb = kernels.letterbox(want_proc, geo)
+    proc, lb = eng.preprocess_stage(frames)
+    assert proc.shape == (S, h, w, 3) and lb.shape == (S, geo[0], geo[1], 3)
+    np.testing.assert_array_equal(proc.cpu().numpy(), want_proc.cpu().numpy())
+    np.testing.assert_array_equal(lb.cpu().numpy(), want_lb.cpu().numpy())
+    own = torch.zeros_like(frames)  # the caller-owned form a recorded schedule uses
+    proc2, lb2 = eng.preprocess_stage(frames, proc=own)
+    assert proc2 is own
+    np.testing.assert_array_equal(own.cpu().numpy(), want_proc.cpu().numpy())
+    np.testing.assert_array_equal(lb2.cpu().numpy(), want_lb.cpu().numpy())
+    np.testing.assert_array_equal(frames.cpu().numpy(), host)  # inputs untouched
+    eng.close()
 
 
 def test_custom_op_chain_needs_eager_mode(cuda, inputs):

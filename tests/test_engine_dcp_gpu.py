@@ -35,6 +35,7 @@ def _key(res):
 
 
 def test_recorded_pipeline_runs_the_dcp_chain(cuda):
+    from rvs_amd import kernels
     from rvs_amd.engine import RoadVisionEngine
     from rvs_amd.preprocess.ops import dcp_params
     from rvs_amd.schedule import PipelinedRun
@@ -48,7 +49,8 @@ def test_recorded_pipeline_runs_the_dcp_chain(cuda):
                  for k in range(K)]
 
     seq = RoadVisionEngine(cfg, S, (H, W), device=cuda)
-    assert not seq.fused_letterbox and seq.pipeline.chain_supported
+    assert seq.pipeline.chain_supported
+    assert seq.pipeline.chain_route(H, W, seq.detector.geo) == kernels.ROUTE_OPS
     seq_res, seq_proc = [], []
     for r in range(2):
         for k in range(K):

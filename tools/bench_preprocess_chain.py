@@ -13,7 +13,7 @@ the host read as well: that stall is part of what the form costs a stream.
 The eager pipeline returns the input tensor itself for frames it passes
 through; a recorded stage needs proc in its own buffer, so both forms are
 also timed writing a caller-owned proc ("into": the eager form plus the copy
-RoadVisionEngine.preprocess_into made).
+RoadVisionEngine.preprocess_stage(proc=...) makes on its eager fallback).
 
     python3 tools/bench_preprocess_chain.py [--out profiles/r07/preprocess_chain.json]
 """
@@ -146,7 +146,7 @@ def main():
 
         def old_into():
             # ... into a caller-owned proc buffer, as a schedule's stage needs it
-            # (RoadVisionEngine.preprocess_into: proc.copy_(p))
+            # (RoadVisionEngine.preprocess_stage(proc=...): proc.copy_(p))
             p, _ = eager_form(x, ops, enabled, gate_on, 20.0, geo, lb_old)
             out_old.copy_(p)
 

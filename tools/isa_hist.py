@@ -1,7 +1,7 @@
 """Static instruction histogram of one kernel in a hipcc -S assembly file.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
-          --cuda-device-only -S csrc/preprocess.hip -o /tmp/pp.s
+          --cuda-device-only -S csrc/median.hip -o /tmp/pp.s
     python tools/isa_hist.py /tmp/pp.s med3_kernelILb1ELb1E [--blocks]
 
 Counts are static (per instruction in the listing), so loop bodies count
