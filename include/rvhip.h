@@ -621,6 +621,16 @@ int rv_candidates_from_raw(const float* raw, int B, int nc, int A, float conf, v
 /* ------------------------------------------------------------------------ */
 size_t rv_sort_state_bytes(int S, int tmax);
 size_t rv_sort_ws_bytes(int S, int tmax, int dmax);
+/* ByteTrack's second association threshold (Zhang et al., ECCV 2022: the
+ * hard-coded 0.5 of BYTE's second matching); not configurable. */
+#define RV_BYTE_SECOND_IOU 0.5
+/* Host query: byte offsets, inside a workspace of rv_sort_ws_bytes(S, tmax,
+ * dmax), of the two regions a BYTE update (params6[5] > 0, below) writes:
+ * the kept rows (S x dmax x 6 f32) and the kept counts (S int32).  Both are
+ * 256-byte aligned and disjoint from everything else in the workspace, so
+ * they hold one update's result until the next update on that workspace.  A
+ * plain update (params6[5] == 0) writes neither. */
+int rv_sort_kept_layout(int S, int tmax, int dmax, size_t* dets_off, size_t* n_off);
 /* Zero the state (no tracks, next_id = 1); synchronises `stream`.  Layout:
  * per-stream headers, list orders (tmax int32 each) and track pools (tmax
  * slots each); a track keeps its slot for life, the reference's list order
@@ -632,13 +642,33 @@ int rv_sort_init(void* state, int S, int tmax, void* stream);
  * pass state_in == state_out (if they differ, state_in is first copied to
  * state_out).  dets: S x dmax x 6 {x1,y1,x2,y2,conf,cls} f32 (post
  * class-filter), dcount[S]; ts[S] seconds.  params6 = {max_staleness,
- * min_hits, iou_threshold, speed_window, max_distance (<0 = None), 0}.  H9
+ * min_hits, iou_threshold, speed_window, max_distance (<0 = None),
+ * track_high_thresh (0 = plain SORT; see BYTE below)}.  H9
  * (nullable = no projector): row-major f64 homography; origin2: projector
  * origin (f32).  Outputs per detection (S x dmax): track id (-1 = None),
  * distance_m and speed_kmh (NaN = None); a new track that is dropped in the
  * same frame (max_staleness < 0, or no free slot) still reports its id and
  * its box's distance, as the reference does.  tmax <= 8192 and the association
- * workgroup's LDS (about 41 B x tmax + 28 B x dmax + 32 KB) <= 160 KB. */
+ * workgroup's LDS (about 41 B x tmax + 28 B x dmax + 32 KB; with BYTE about
+ * 42 B x tmax + 33 B x dmax + 32 KB) <= 160 KB.
+ *
+ * BYTE (params6[5] = track_high_thresh in (0, 1]): ByteTrack's second
+ * association on this SORT, in the one-launch (fused) form only.  A row is
+ * high iff (double)conf >= track_high_thresh, else low (the caller has
+ * removed the rows below its track_low_thresh).  Stage 1: the greedy
+ * association of all tracks with the high rows at iou_threshold.  Stage 2:
+ * the same greedy loop over the tracks stage 1 left unmatched whose
+ * hit_streak was > 0 before this frame and the low rows, at
+ * RV_BYTE_SECOND_IOU.  A stage-2 match is an ordinary match.  New tracks come
+ * from unmatched high rows only; unmatched low rows are dropped.  The kept
+ * rows (every high row and every matched low row, in input order) and their
+ * count go to the workspace regions of rv_sort_kept_layout, rows at or beyond
+ * the count zero; out_id / out_dist / out_speed are indexed by kept row, and
+ * rows at or beyond the count are -1 / NaN / NaN.  dets is not modified.
+ * With every row high the results are the plain update's, bit for bit.
+ * params6[5] outside [0, 1] or NaN, or > 0 with RV_SORT_FUSED=0 (the
+ * three-launch form has no second association): RV_EINVAL.  A recorded
+ * schedule carries the mode in the 48-byte copy of params6. */
 int rv_sort_update(void* state_in, void* state_out, int S, int tmax, const float* dets,
                    const int* dcount, int dmax, const double* ts, const double* params6,
                    const double* H9, const float* origin2, void* ws, size_t ws_bytes,

@@ -432,14 +432,20 @@ constexpr int kAssocThreads = RV_ASSOC_THREADS;
 // (kKeyCap u64), tupd (tmax f64), det_match (dmax), trk_match / ord / rank_t
 // / frank (tmax int each), rank_d / newslot (dmax int each), used (tmax u8);
 // the fused form adds the KF update scratch (kUpd x 126 f64, from offset 0)
-// and the detection jobs (dmax int2) at sort_ljob_off.
+// and the detection jobs (dmax int2) at sort_ljob_off.  The BYTE instances
+// add, behind `used`, the detections' class bytes (dmax u8: 1 = high) and the
+// tracks' eligibility bytes (tmax u8: hit_streak > 0 before this frame) and,
+// behind the jobs, the kept rank of every row (dmax int, padded to 8 bytes).
 constexpr int kUpdLanes = 64;
-__host__ __device__ inline size_t sort_assoc_bytes(int tmax, int dmax) {
+__host__ __device__ inline size_t sort_assoc_bytes(int tmax, int dmax, bool byte = false) {
   return (size_t)(tmax + dmax) * 16 + (size_t)kKeyCap * 8 + (size_t)tmax * 8 + (size_t)dmax * 4 * 3 +
-         (size_t)tmax * 4 * 4 + (size_t)tmax;
+         (size_t)tmax * 4 * 4 + (size_t)tmax + (byte ? (size_t)tmax + (size_t)dmax : 0);
 }
-__host__ __device__ inline size_t sort_ljob_off(int tmax, int dmax, int kupd) {
-  const size_t a = (sort_assoc_bytes(tmax, dmax) + 15) & ~(size_t)15;
+__host__ __device__ inline size_t sort_krank_bytes(int dmax) {
+  return ((size_t)dmax * 4 + 7) & ~(size_t)7;
+}
+__host__ __device__ inline size_t sort_ljob_off(int tmax, int dmax, int kupd, bool byte = false) {
+  const size_t a = (sort_assoc_bytes(tmax, dmax, byte) + 15) & ~(size_t)15;
   // kKfScratch doubles per update lane, or (the row-parallel update, at
   // most kupd detections) kKfRows doubles per detection
   const size_t b = (size_t)kupd * (kKfRows > 126 ? kKfRows : 126) * 8;
@@ -500,18 +506,21 @@ __device__ int block_rank(F flag, int n, int* out, int* wtot) {
 // a track's stored distance / speed are handed out also while the stream has
 // no projector, as sort_tracker.py:242-247 does when a call's projector is
 // None (a matched track keeps its last values; a new track's are None).
+// orow: the row of the three outputs (the BYTE instances: the row's kept rank;
+// else d itself).
 template <bool KEEP>
 __device__ __forceinline__ void sort_update_row(Track* __restrict__ pool, const float* __restrict__ dets,
-                                                double ts, int s, int d, int2 j, const SortParams& p,
-                                                int* __restrict__ out_id, double* __restrict__ out_dist,
+                                                double ts, int s, int d, int orow, int2 j,
+                                                const SortParams& p, int* __restrict__ out_id,
+                                                double* __restrict__ out_dist,
                                                 double* __restrict__ out_speed, double* ap,
                                                 int ap_stride, bool kf_done = false) {
-  const size_t o = (size_t)s * p.dmax + d;
+  const size_t o = (size_t)s * p.dmax + orow;
   out_id[o] = -1;
   out_dist[o] = NAN;
   out_speed[o] = NAN;
   if (j.x == -2) return;  // no detection
-  const float* de = dets + o * 6;
+  const float* de = dets + ((size_t)s * p.dmax + d) * 6;
   if (j.x < 0) {  // a new track that did not fit or was pruned at once: the id is still consumed
     out_id[o] = j.y;
     // the reference runs update_metrics on the new track before it drops it
@@ -584,15 +593,40 @@ __device__ unsigned long long g_sort_phase[8];
 // phase takes its parameters from there, so the serial f64 chain of the
 // update never waits on HBM for the table and nothing is held in registers
 // across the association.
-template <int NT, bool FUSED, class PT = SortParams>
+//
+// BYTE (FUSED only; params6[5] = track_high_thresh > 0): ByteTrack's second
+// association on the reference's SORT.  A detection is high iff (double)conf
+// >= high, else low.  Stage 1 is the association above over (all tracks) x
+// (high detections) at iou_threshold; stage 2 is the same greedy loop over
+// (tracks stage 1 left unmatched whose hit_streak was > 0 before this frame)
+// x (low detections) at RV_BYTE_SECOND_IOU.  Both go through the same three
+// sorters.  The key stays (IoU desc, full flat index t * D + d asc): the
+// tracks and the detections of either stage are ascending subsets of the
+// list and of the rows, so the order of the full flat indices of a stage's
+// pairs is the row-major order of its sub-matrix, and the first maximum of
+// the sub-matrix (numpy's argmax) is the smallest full flat index among the
+// maxima.  New tracks come from unmatched high rows only; the kept rows
+// (high or matched) are compacted in input order into the caller's workspace
+// (rv_sort_kept_layout) and the three outputs are indexed by kept rank.
+// The BYTE instances' launch parameters: PT plus the threshold and the kept
+// regions (the plain instances take PT itself: their arguments do not change).
+template <class PT>
+struct WithByte : PT {
+  double high;    // track_high_thresh
+  float* kept;    // S x dmax x 6: the kept rows, rows >= kept_n[s] zero
+  int* kept_n;    // S
+};
+
+template <int NT, bool FUSED, class PT = SortParams, bool BYTE = false>
 __global__ __launch_bounds__(NT) void sort_associate_kernel(
     StreamHdr* __restrict__ hdr, int* __restrict__ order, Track* __restrict__ pool,
     const float* __restrict__ dets, const int* __restrict__ dcount,
-    const double* __restrict__ ts_arr, PT p, SortWs ws, int* __restrict__ out_id,
-    double* __restrict__ out_dist, double* __restrict__ out_speed) {
+    const double* __restrict__ ts_arr, std::conditional_t<BYTE, WithByte<PT>, PT> p, SortWs ws,
+    int* __restrict__ out_id, double* __restrict__ out_dist, double* __restrict__ out_speed) {
   constexpr int kAssocThreads = NT;
   constexpr bool CAMS = !std::is_same<PT, SortParams>::value;
   static_assert(!CAMS || FUSED, "the camera table is read by the kernel that runs the metrics");
+  static_assert(!BYTE || FUSED, "the second association exists in the fused form only");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int kUpd = NT < kUpdLanes ? NT : kUpdLanes;  // FUSED: threads running the KF updates
   float4* tbox = (float4*)smem;                     // tmax
@@ -610,9 +644,16 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
   // FUSED: the detection jobs, after `used` and after the KF update
   // scratch (kUpd x 126 doubles, which reuses the dead association arrays
   // from offset 0 once the bookkeeping is done)
-  int2* ljob = (int2*)(smem + sort_ljob_off(p.tmax, p.dmax, kUpd));
+  int2* ljob = (int2*)(smem + sort_ljob_off(p.tmax, p.dmax, kUpd, BYTE));
+  // BYTE: class byte per detection, eligibility byte per track (behind
+  // `used`); the kept rank of every row behind the jobs (it outlives the
+  // association arrays, which the KF update scratch overwrites)
+  uint8_t* dcls = used + p.tmax;  // dmax
+  uint8_t* elig = dcls + p.dmax;  // tmax
+  int* krank = (int*)(ljob + p.dmax);
   // CAMS: the parameters with the stream's projector, behind the jobs (8-byte aligned)
-  SortParams* lpar = (SortParams*)(ljob + p.dmax);
+  SortParams* lpar =
+      (SortParams*)((uint8_t*)(ljob + p.dmax) + (BYTE ? sort_krank_bytes(p.dmax) : (size_t)0));
   __shared__ int s_cnt, s_red_v[16], s_red_i[16], wtot[16];
 
   const int s = blockIdx.x;
@@ -651,6 +692,7 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
     const int slot = ord_g[t];
     if constexpr (FUSED) {  // sort_predict_kernel's work for list index t
       Track& tr = pl[slot];
+      if constexpr (BYTE) elig[t] = tr.streak > 0 ? 1 : 0;  // "Tracked, not Lost"
       kf_predict(tr, ts - tr.t_pred);
       tr.t_pred = ts;
       tbox[t] = x_to_bbox(tr.x);
@@ -665,170 +707,33 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
   for (int d = tid; d < D; d += kAssocThreads) {
     dbox[d] = make_float4(dd[d * 6], dd[d * 6 + 1], dd[d * 6 + 2], dd[d * 6 + 3]);
     det_match[d] = -1;
+    if constexpr (BYTE) dcls[d] = (double)dd[d * 6 + 4] >= p.high ? 1 : 0;
   }
   if (tid == 0) s_cnt = 0;
   __syncthreads();
   RV_PH(0);  // predict + loads
 
-  // ---- association (_associate, sort_tracker.py:182-210)
-  if (T > 0 && D > 0) {
-    // qualifying pairs appended with one LDS atomic per wave (a ballot's
-    // popcount), not one per pair; the append order does not matter (the
-    // keys are sorted next and unique)
-    // pair i = tid + kAssocThreads k is (i / D, i % D), stepped
-    // incrementally (an integer division by the runtime D per pair was ~20
-    // VALU, as much as the IoU itself)
-    const int dt = kAssocThreads / D, dd = kAssocThreads - (kAssocThreads / D) * D;
-    int pt = tid / D, pd = tid - (tid / D) * D;
-    for (int i0 = 0; i0 < T * D; i0 += kAssocThreads) {
-      const int i = i0 + tid;
-      bool q = false;
-      float v = 0.f;
-      if (i < T * D) {
-        v = iou_f32(tbox[pt], dbox[pd]);
-        q = (double)v >= p.iou_thr;
-      }
-      pt += dt;
-      pd += dd;
-      if (pd >= D) {
-        pd -= D;
-        ++pt;
-      }
-      const unsigned long long m = __ballot(q);
-      if (m) {  // wave-uniform
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&s_cnt, __popcll(m));
-        base = __shfl(base, 0);
-        if (q) {
-          const int k = base + __popcll(m & ((1ull << lane) - 1ull));
-          if (k < kKeyCap) keys[k] = ((uint64_t)(~__float_as_uint(v)) << 32) | (uint64_t)(uint32_t)i;
-        }
-      }
-    }
-    __syncthreads();
-    RV_PH(1);  // IoU pairs
-    const int cnt = s_cnt;
-    if (cnt <= kKeyCap) {
-      int np2 = 1;
-      while (np2 < cnt) np2 <<= 1;
-      if (cnt <= kAssocThreads) {
-        // rank sort: key i lands at the number of smaller keys (unique:
-        // the flat index is in the low bits); every thread reads the same
-        // key at once (an LDS broadcast) -- cnt reads and two barriers
-        // instead of log2(np2)^2 / 2 bitonic stages
-        const uint64_t mine = tid < cnt ? keys[tid] : ~0ull;
-        int r = 0;
-        for (int j = 0; j < cnt; ++j) r += keys[j] < mine ? 1 : 0;
-        __syncthreads();
-        if (tid < cnt) keys[r] = mine;
-        __syncthreads();
-        np2 = 0;  // sorted
-      }
-      for (int i = cnt + tid; i < np2; i += kAssocThreads) keys[i] = ~0ull;
-      __syncthreads();
-      for (int size = 2; size <= np2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-          for (int i = tid; i < np2 / 2; i += kAssocThreads) {
-            const int lo = 2 * i - (i & (stride - 1));
-            const int hi = lo + stride;
-            const bool up = (lo & size) == 0;
-            const uint64_t a = keys[lo], c = keys[hi];
-            if ((a > c) == up) {
-              keys[lo] = c;
-              keys[hi] = a;
-            }
-          }
-          __syncthreads();
-        }
-      RV_PH(2);  // sort
-      // greedy walk in (IoU desc, flat index asc) order, 64 pairs at a time:
-      // a pair is accepted iff its row and column are still free; inside a
-      // chunk the lowest remaining lane is accepted and the lanes sharing its
-      // row or column are dropped (wave-uniform ballot loop)
-      if (tid < 64) {
-        for (int base = 0; base < cnt; base += 64) {
-          const int i = base + lane;
-          int t = -1, d = -2;
-          bool ok = false;
-          if (i < cnt) {
-            const int f = (int)(keys[i] & 0xFFFFFFFFu);
-            t = f / D;
-            d = f - t * D;
-            ok = trk_match[t] < 0 && det_match[d] < 0;
-          }
-          unsigned long long m = __ballot(ok);
-          while (m) {
-            const int q = __ffsll((long long)m) - 1;
-            const int tq = __shfl(t, q), dq = __shfl(d, q);
-            if (lane == q) {
-              trk_match[t] = d;
-              det_match[d] = t;
-            }
-            m &= ~__ballot(t == tq || d == dq);
-          }
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-    } else {
-      // more qualifying pairs than keys: the literal reference loop (argmax
-      // with the first maximum, accept, mask row and column) over M in HBM
-      float* M = ws.M + (size_t)s * p.tmax * p.dmax;
-      for (int i = tid; i < T * D; i += kAssocThreads) {
-        const int t = i / D, d = i - (i / D) * D;
-        M[i] = iou_f32(tbox[t], dbox[d]);
-      }
-      __syncthreads();
-      for (;;) {
-        float bv = -INFINITY;
-        int bi = 0x7FFFFFFF;
-        for (int i = tid; i < T * D; i += kAssocThreads) {
-          const float v = M[i];
-          if (v > bv || (v == bv && i < bi)) {
-            bv = v;
-            bi = i;
-          }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-          const float ov = __shfl_xor(bv, off);
-          const int oi = __shfl_xor(bi, off);
-          if (ov > bv || (ov == bv && oi < bi)) {
-            bv = ov;
-            bi = oi;
-          }
-        }
-        if (lane == 0) {
-          s_red_v[tid >> 6] = __float_as_int(bv);
-          s_red_i[tid >> 6] = bi;
-        }
-        __syncthreads();
-        bv = __int_as_float(s_red_v[0]);
-        bi = s_red_i[0];
-        for (int w = 1; w < kAssocThreads / 64; ++w) {
-          const float ov = __int_as_float(s_red_v[w]);
-          if (ov > bv || (ov == bv && s_red_i[w] < bi)) {
-            bv = ov;
-            bi = s_red_i[w];
-          }
-        }
-        __syncthreads();
-        if ((double)bv < p.iou_thr) break;
-        const int t = bi / D, d = bi - (bi / D) * D;
-        if (tid == 0) {
-          trk_match[t] = d;
-          det_match[d] = t;
-        }
-        for (int j = tid; j < D; j += kAssocThreads) M[t * D + j] = -1.0f;
-        for (int i = tid; i < T; i += kAssocThreads) M[i * D + d] = -1.0f;
-        __syncthreads();
-      }
-    }
+  // ---- association (_associate, sort_tracker.py:182-210); BYTE: twice, the
+  // second time over what the first left (see above the kernel)
+  {
+    constexpr int stage = 0;
+#include "sort_assoc_stage.h"
+  }
+  if constexpr (BYTE) {
+    constexpr int stage = 1;
+#include "sort_assoc_stage.h"
   }
   __syncthreads();
   RV_PH(3);  // greedy walk (or the fallback loop)
 
   // ---- bookkeeping (sort_tracker.py:234-276)
-  const int n_new = block_rank<NT>([&](int d) { return det_match[d] < 0; }, D, rank_d, wtot);
+  // BYTE: new tracks come from the unmatched high rows only; the kept rows
+  // are the high and the matched ones, in input order
+  const int n_new = block_rank<NT>(
+      [&](int d) { return det_match[d] < 0 && (!BYTE || dcls[d] != 0); }, D, rank_d, wtot);
+  int n_kept = 0;
+  if constexpr (BYTE)
+    n_kept = block_rank<NT>([&](int d) { return det_match[d] >= 0 || dcls[d] != 0; }, D, krank, wtot);
   const int n_surv = block_rank<NT>(
       [&](int t) {
         const double upd = trk_match[t] >= 0 ? ts : tupd[t];
@@ -868,7 +773,7 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
       const int t = det_match[d];
       if (t >= 0) {
         j = make_int2(ord[t], -1);
-      } else {
+      } else if (!BYTE || dcls[d] != 0) {  // (BYTE: an unmatched low row is dropped)
         const int r = rank_d[d];
         j = make_int2(r < n_fit ? newslot[r] : -1, h.next_id + r);
       }
@@ -886,6 +791,24 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
     o.pad = 0;
     hdr[s] = o;
   }
+  if constexpr (BYTE) {
+    // the kept rows and their count; rows [n_kept, dmax) of the kept rows and
+    // of the three outputs are empty (the update phase writes rows < n_kept)
+    float* kd = p.kept + (size_t)s * p.dmax * 6;
+    for (int d = tid; d < D; d += NT) {
+      const int k = krank[d];
+      if (k >= 0)
+        for (int c = 0; c < 6; ++c) kd[k * 6 + c] = dd[d * 6 + c];
+    }
+    for (int e = n_kept + tid; e < p.dmax; e += NT) {
+      const size_t o = (size_t)s * p.dmax + e;
+      for (int c = 0; c < 6; ++c) kd[e * 6 + c] = 0.f;
+      out_id[o] = -1;
+      out_dist[o] = NAN;
+      out_speed[o] = NAN;
+    }
+    if (tid == 0) p.kept_n[s] = n_kept;
+  }
   if constexpr (FUSED) {
     // sort_update_kernel's work: the streak resets above and the predicted
     // states are this block's own global writes, visible after the barrier
@@ -902,24 +825,31 @@ __global__ __launch_bounds__(NT) void sort_associate_kernel(
       const int d = tid >> 3, r = tid & 7;
       const int2 j = d < D ? ljob[d] : make_int2(-2, -1);
       const bool matched = d < D && j.x >= 0 && j.y < 0;
+      int orow = d;  // BYTE: the row's kept rank, < 0 = dropped (no outputs)
+      if constexpr (BYTE) orow = d < D ? krank[d] : -1;
       if (matched) {
         double z[4];
         const float* de = dets + ((size_t)s * p.dmax + d) * 6;
         bbox_to_z(de[0], de[1], de[2], de[3], z);
         kf_update_rows(pl[j.x], z, (double*)smem + (size_t)d * kKfRows, r);
       }
-      if (r == 0 && d < D)
-        sort_update_row<CAMS>(pool, dets, ts, s, d, j, q, out_id, out_dist, out_speed, nullptr, 0,
-                              matched);
-      for (int e = D + tid; e < p.dmax; e += NT)
-        sort_update_row<CAMS>(pool, dets, ts, s, e, ljob[e], q, out_id, out_dist, out_speed,
-                              nullptr, 0);
+      if (r == 0 && d < D && orow >= 0)
+        sort_update_row<CAMS>(pool, dets, ts, s, d, orow, j, q, out_id, out_dist, out_speed,
+                              nullptr, 0, matched);
+      if constexpr (!BYTE)
+        for (int e = D + tid; e < p.dmax; e += NT)
+          sort_update_row<CAMS>(pool, dets, ts, s, e, e, ljob[e], q, out_id, out_dist, out_speed,
+                                nullptr, 0);
     } else {
       double* ap = (double*)smem + tid;
       if (tid < kUpd)
-        for (int d = tid; d < p.dmax; d += kUpd)
-          sort_update_row<CAMS>(pool, dets, ts, s, d, ljob[d], q, out_id, out_dist, out_speed, ap,
-                                kUpd);
+        for (int d = tid; d < (BYTE ? D : p.dmax); d += kUpd) {
+          int orow = d;
+          if constexpr (BYTE) orow = krank[d];
+          if (orow >= 0)
+            sort_update_row<CAMS>(pool, dets, ts, s, d, orow, ljob[d], q, out_id, out_dist,
+                                  out_speed, ap, kUpd);
+        }
     }
     RV_PH(5);  // KF updates + metrics
   }
@@ -946,7 +876,7 @@ __global__ __launch_bounds__(kUpdLanes) void sort_update_kernel(
   const int s = blockIdx.y;
   const int d = blockIdx.x * kUpdLanes + threadIdx.x;
   if (d >= p.dmax) return;
-  sort_update_row<false>(pool, dets, ts_arr[s], s, d, ws.det_job[(size_t)s * p.dmax + d], p,
+  sort_update_row<false>(pool, dets, ts_arr[s], s, d, d, ws.det_job[(size_t)s * p.dmax + d], p,
                          out_id, out_dist, out_speed, ap + threadIdx.x, kUpdLanes);
 }
 
@@ -969,7 +899,7 @@ __global__ __launch_bounds__(kUpdLanes) void sort_update_cams_kernel(
     p.has_proj = cam.enabled;
   }
   if (d >= p.dmax) return;
-  sort_update_row<true>(pool, dets, ts_arr[s], s, d, ws.det_job[(size_t)s * p.dmax + d], p,
+  sort_update_row<true>(pool, dets, ts_arr[s], s, d, d, ws.det_job[(size_t)s * p.dmax + d], p,
                         out_id, out_dist, out_speed, ap + threadIdx.x, kUpdLanes);
 }
 
@@ -1033,7 +963,8 @@ extern "C" size_t rv_sort_state_bytes(int S, int tmax) {
          (size_t)S * tmax * sizeof(Track);
 }
 
-// M (argmax fallback) + predicted boxes + last_update_ts + detection jobs
+// M (argmax fallback) + predicted boxes + last_update_ts + detection jobs +
+// the BYTE instances' kept rows and kept counts (rv_sort_kept_layout)
 static size_t ws_parts(int S, int tmax, int dmax, size_t* off) {
   size_t o = 0;
   off[0] = o;
@@ -1044,19 +975,35 @@ static size_t ws_parts(int S, int tmax, int dmax, size_t* off) {
   o = align256(o + (size_t)S * tmax * sizeof(double));
   off[3] = o;
   o = align256(o + (size_t)S * dmax * sizeof(int2));
+  off[4] = o;
+  o = align256(o + (size_t)S * dmax * 6 * sizeof(float));
+  off[5] = o;
+  o = align256(o + (size_t)S * sizeof(int));
   return o;
 }
 
 extern "C" size_t rv_sort_ws_bytes(int S, int tmax, int dmax) {
   if (S <= 0 || tmax <= 0 || dmax <= 0) return 0;
-  size_t off[4];
+  size_t off[6];
   return ws_parts(S, tmax, dmax, off);
 }
 
+extern "C" int rv_sort_kept_layout(int S, int tmax, int dmax, size_t* dets_off, size_t* n_off) {
+  RV_CHECK_ARG(S > 0 && tmax > 0 && dmax > 0, "bad sizes");
+  RV_CHECK_ARG(dets_off && n_off, "null pointer");
+  size_t off[6];
+  ws_parts(S, tmax, dmax, off);
+  *dets_off = off[4];
+  *n_off = off[5];
+  return RV_OK;
+}
+
 constexpr int kFusedThreads = RV_SORT_FUSED_THREADS;
-static size_t sort_smem(int tmax, int dmax, bool fused) {
+static size_t sort_smem(int tmax, int dmax, bool fused, bool byte = false) {
   const int kupd = kFusedThreads < kUpdLanes ? kFusedThreads : kUpdLanes;
-  return fused ? sort_ljob_off(tmax, dmax, kupd) + (size_t)dmax * 8 : sort_assoc_bytes(tmax, dmax);
+  return fused ? sort_ljob_off(tmax, dmax, kupd, byte) + (size_t)dmax * 8 +
+                     (byte ? sort_krank_bytes(dmax) : 0)
+               : sort_assoc_bytes(tmax, dmax);
 }
 
 // RV_SORT_FUSED=0: the three-launch form (A/B)
@@ -1098,6 +1045,14 @@ static int sort_update_any(void* state_in, void* state_out, int S, int tmax, con
   RV_CHECK_ARG(ws_bytes >= rv_sort_ws_bytes(S, tmax, dmax), "workspace too small");
   RV_CHECK_ARG((size_t)tmax * dmax < 0xFFFFFFFFull, "tmax*dmax too large");
   RV_CHECK_ARG(((uintptr_t)cams & 7) == 0, "cams is not 8-byte aligned");
+  // params6 is read only now, behind every check of the other arguments
+  const double high = params6[5];
+  RV_CHECK_ARG(high >= 0.0 && high <= 1.0, "track_high_thresh (params6[5]) %g is not in [0, 1]", high);
+  const bool fused = sort_fused();
+  const bool byte = high > 0.0;
+  RV_CHECK_ARG(!byte || fused,
+               "track_high_thresh > 0 (the second association) needs the fused form: "
+               "RV_SORT_FUSED=0 has no BYTE kernel");
   SortParamsCams p;
   memset(&p, 0, sizeof(p));
   p.max_staleness = params6[0];
@@ -1115,9 +1070,9 @@ static int sort_update_any(void* state_in, void* state_out, int S, int tmax, con
     p.origin[0] = origin2[0];
     p.origin[1] = origin2[1];
   }
-  const bool fused = sort_fused();
   // the fused cams kernel keeps its stream's parameters behind the jobs
-  const size_t smem = sort_smem(tmax, dmax, fused) + (use_cams && fused ? sizeof(SortParams) : 0);
+  const size_t smem =
+      sort_smem(tmax, dmax, fused, byte) + (use_cams && fused ? sizeof(SortParams) : 0);
   RV_CHECK_ARG(smem <= 160 * 1024, "tmax/dmax need %zu B of LDS", smem);
   hipStream_t st = as_stream(stream);
   int r = RV_OK;
@@ -1128,11 +1083,14 @@ static int sort_update_any(void* state_in, void* state_out, int S, int tmax, con
   if (r) return r;
   // the association kernel that runs: [0] three-launch, [1] fused, [2] fused
   // with the camera table (the three-launch form reads the table in its
-  // update kernel, so its association kernel is [0] either way)
-  static int attr_set[3] = {0, 0, 0};
-  const int form = fused ? (use_cams ? 2 : 1) : 0;
+  // update kernel, so its association kernel is [0] either way); [3], [4]:
+  // the BYTE instances of [1], [2]
+  static int attr_set[5] = {0, 0, 0, 0, 0};
+  const int form = byte ? (use_cams ? 4 : 3) : fused ? (use_cams ? 2 : 1) : 0;
   const void* assoc_fn =
-      form == 2   ? (const void*)sort_associate_kernel<kFusedThreads, true, SortParamsCams>
+      form == 4 ? (const void*)sort_associate_kernel<kFusedThreads, true, SortParamsCams, true>
+      : form == 3 ? (const void*)sort_associate_kernel<kFusedThreads, true, SortParams, true>
+      : form == 2 ? (const void*)sort_associate_kernel<kFusedThreads, true, SortParamsCams>
       : form == 1 ? (const void*)sort_associate_kernel<kFusedThreads, true>
                   : (const void*)sort_associate_kernel<kAssocThreads, false>;
   if ((int)smem > attr_set[form]) {  // once per growth, outside steady-state launches
@@ -1145,7 +1103,7 @@ static int sort_update_any(void* state_in, void* state_out, int S, int tmax, con
     attr_set[form] = (int)smem;
   }
   const StateView v = state_view(state_out, S, tmax);
-  size_t off[4];
+  size_t off[6];
   ws_parts(S, tmax, dmax, off);
   SortWs w;
   w.M = (float*)((uint8_t*)ws + off[0]);
@@ -1153,6 +1111,21 @@ static int sort_update_any(void* state_in, void* state_out, int S, int tmax, con
   w.tupd = (double*)((uint8_t*)ws + off[2]);
   w.det_job = (int2*)((uint8_t*)ws + off[3]);
   const SortParams& pb = p;  // the launch parameters without the table
+  if (byte) {
+    float* kept = (float*)((uint8_t*)ws + off[4]);
+    int* kept_n = (int*)((uint8_t*)ws + off[5]);
+    if (use_cams) {
+      const WithByte<SortParamsCams> bp{p, high, kept, kept_n};
+      sort_associate_kernel<kFusedThreads, true, SortParamsCams, true>
+          <<<S, kFusedThreads, smem, st>>>(v.hdr, v.order, v.pool, dets, dcount, ts, bp, w,
+                                           out_id, out_dist, out_speed);
+      return launch_status("rv_sort_update_cams (fused, BYTE)");
+    }
+    const WithByte<SortParams> bp{pb, high, kept, kept_n};
+    sort_associate_kernel<kFusedThreads, true, SortParams, true><<<S, kFusedThreads, smem, st>>>(
+        v.hdr, v.order, v.pool, dets, dcount, ts, bp, w, out_id, out_dist, out_speed);
+    return launch_status("rv_sort_update (fused, BYTE)");
+  }
   if (form == 2) {
     sort_associate_kernel<kFusedThreads, true, SortParamsCams><<<S, kFusedThreads, smem, st>>>(
         v.hdr, v.order, v.pool, dets, dcount, ts, p, w, out_id, out_dist, out_speed);

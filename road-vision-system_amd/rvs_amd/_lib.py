@@ -211,6 +211,8 @@ _SIGS = {
     # track
     "rv_sort_state_bytes": (c_size_t, [c_int, c_int]),
     "rv_sort_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    # offsets of the BYTE kept rows / kept counts in the workspace (host query)
+    "rv_sort_kept_layout": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "rv_sort_init": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "rv_sort_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -20,6 +20,8 @@ _DEFAULTS = {
     "detect": {"enabled": False, "backend": "ultralytics", "model": "yolov8n.pt",
                "device": "auto", "conf_thres": 0.25, "iou_thres": 0.7, "max_det": 100,
                "classes_keep": []},
+    # backend "bytetrack": also track_high_thresh (default detect.conf_thres)
+    # and track_low_thresh (default 0.1), read with .get by the engine
     "tracking": {"enabled": False, "backend": "sort", "max_staleness": 1.0, "min_hits": 3,
                  "iou_threshold": 0.3, "speed_window": 0.75},
     "geometry": {"enabled": False,

@@ -26,6 +26,8 @@ from .geometry import GroundProjector, build_camera_projectors, build_projector
 from .handback import Record, handback
 from .io_video.sink import MultiStreamSink, record_settings
 from .preprocess import PreprocessPipeline
+from .track.byte_hip import MultiStreamByte, byte_thresholds
+from .track.registry import BYTE_BACKENDS, backend_name
 from .track.sort_hip import CameraTable, MultiStreamSort
 from .vis.display_list import canvas_geometry
 from .vis.overlay import OverlayRenderer
@@ -48,7 +50,22 @@ class RoadVisionEngine:
         B = 64: 20.5 us per frame against 25.0 at B = 32,
         tools/probe_batch.py).  Every stream still sees its frames in order
         in SORT, so results are those of sequential step() calls; a frame's
-        results come out P - 1 steps later."""
+        results come out P - 1 steps later.
+
+        tracking.backend "bytetrack" / "byte" / "bytetrack_hip": the tracker
+        is MultiStreamByte (ByteTrack's second association on low-score
+        detections, track/byte_hip.py) and the detector runs at conf =
+        tracking.track_low_thresh instead of detect.conf_thres, so the low
+        rows reach the tracker.  NMS never lets a lower score suppress a
+        higher one and its output is score-ordered, so the rows at or above
+        tracking.track_high_thresh (default: detect.conf_thres) are the rows
+        the SORT configuration would see -- as long as an image has at most
+        detect.max_det rows at conf = low; beyond that NMS cuts the list at
+        max_det either way, and the low rows do not displace high ones (they
+        sort behind them).  Every stage downstream of the tracker (hand-back,
+        overlays, recording, out["dets"] / out["det_n"]) sees the rows the
+        tracker kept, not the NMS output.  0 < low <= high <= 1 is required
+        (ValueError).  Every other backend value builds the SORT tracker."""
         cfg = cfg if cfg is not None else load_config()
         self.cfg = cfg
         self.S = int(n_streams)
@@ -66,6 +83,14 @@ class RoadVisionEngine:
         # their `enabled` key is set (src/config.py defaults both to False)
         self.detect_enabled = bool(det_cfg.get("enabled", False))
         self.tracking_enabled = bool(trk_cfg.get("enabled", False))
+        # tracking.backend: BYTE needs the detector's low rows (a wrong
+        # threshold pair is a configuration error, not a feature to drop)
+        conf_thres = float(det_cfg.get("conf_thres", 0.25))
+        self.byte = self.tracking_enabled and backend_name(trk_cfg) in BYTE_BACKENDS
+        if self.byte:
+            low, high = byte_thresholds(trk_cfg, conf_thres)
+            trk_cfg = dict(trk_cfg, track_low_thresh=low, track_high_thresh=high)
+            conf_thres = low
         self.variant = resolve_model(det_cfg.get("model", "yolov8n.pt"))
         self.detector = None
         # class count and names: the checkpoint's / the config's (detect.nc,
@@ -77,7 +102,7 @@ class RoadVisionEngine:
             self.detector = YoloEngine(
                 self.variant, weights, self.S * self.pair, (self.H, self.W),
                 imgsz=int(det_cfg.get("imgsz", 640)),
-                conf=float(det_cfg.get("conf_thres", 0.25)),
+                conf=conf_thres,
                 iou=float(det_cfg.get("iou_thres", 0.7)),
                 max_det=int(det_cfg.get("max_det", 100)),
                 classes_keep=[int(x) for x in det_cfg.get("classes_keep", [])],
@@ -113,8 +138,8 @@ class RoadVisionEngine:
         self.tracker = None
         if self.tracking_enabled and self.detector is not None:
             try:
-                tracker = MultiStreamSort(trk_cfg, self.S, tmax=tmax, dmax=self.max_det,
-                                          device=self.device)
+                tracker = (MultiStreamByte if self.byte else MultiStreamSort)(
+                    trk_cfg, self.S, tmax=tmax, dmax=self.max_det, device=self.device)
                 if projectors is not None:
                     tracker.set_projectors(projectors)
                 else:
@@ -288,7 +313,7 @@ class RoadVisionEngine:
         then the hand-back of the results into `record` (pinned host)."""
         self._need_detector("track_stage")
         dets, det_n = self.detector.nms(ts.shape[0], slot)
-        tid, dist, spd = self._metrics(dets, det_n, ts)
+        dets, det_n, tid, dist, spd = self._tracked(dets, det_n, ts)
         out = {"dets": dets, "det_n": det_n, "track_id": tid, "distance_m": dist,
                "speed_kmh": spd}
         if record is not None:
@@ -310,8 +335,8 @@ class RoadVisionEngine:
         dets, det_n = self.detector.nms(S * len(ts_list), slot)
         outs = []
         for h, (ts, rec) in enumerate(zip(ts_list, records)):
-            d, n = dets[h * S:(h + 1) * S], det_n[h * S:(h + 1) * S]
-            tid, dist, spd = self._metrics(d, n, ts)
+            d, n, tid, dist, spd = self._tracked(dets[h * S:(h + 1) * S],
+                                                 det_n[h * S:(h + 1) * S], ts)
             handback(d, n, tid, dist, spd, self.rec_stage, rec.host)
             if overlay is not None:
                 self._record_overlay(overlay[h][0], overlay[h][1], (d, n, tid, dist, spd))
@@ -324,8 +349,18 @@ class RoadVisionEngine:
         hand-back into `record` (tracker.update + the .cpu() hand-over of
         main_preview.py:99-109)."""
         self._need_detector("track_handback")
-        tid, dist, spd = self._metrics(dets, det_n, ts)
+        dets, det_n, tid, dist, spd = self._tracked(dets, det_n, ts)
         handback(dets, det_n, tid, dist, spd, self.rec_stage, record.host)
+
+    def _tracked(self, dets: torch.Tensor, det_n: torch.Tensor, ts: torch.Tensor):
+        """One step's NMS output through the tracker -> (rows, counts,
+        track_id, distance_m, speed_kmh) as every later stage takes them: the
+        NMS buffers themselves, or with a BYTE tracker the rows it kept (its
+        workspace views, rewritten by the next update like the results)."""
+        tid, dist, spd = self._metrics(dets, det_n, ts)
+        if self.byte and self.tracker is not None:
+            dets, det_n = self.tracker.kept_dets, self.tracker.kept_n
+        return dets, det_n, tid, dist, spd
 
     def _metrics(self, dets: torch.Tensor, det_n: torch.Tensor, ts: torch.Tensor):
         """(track_id, distance_m, speed_kmh) of one step's NMS output:
