@@ -151,6 +151,36 @@ int rv_dcp_dehaze_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int p
                      int patch, int wq, int tq, int radius, int eq, void* ws,
                      size_t ws_bytes, int32_t* air_out, uint8_t* t_out, void* stream);
 
+/* Directional rain-streak removal (no reference counterpart: the stronger
+ * derain the reference's plugin registry leaves room for; its MedianDerain
+ * blurs every pixel to remove a 1-pixel streak).  Integer arithmetic end to
+ * end, every division a floor division, every window clipped to the frame
+ * (samples outside it are ignored).  With
+ *   g        = the gray of rv_gray_span_u8
+ *   hmin_k, hmax_k = min / max over the columns x - k/2 .. x + k/2 of the row
+ *   o_j      = sgn(j slant) ((|j slant| + 2) >> 2), so o_-j = -o_j
+ *   emin_n(P)(y, x) = min of P(y + j, x + o_j) over j in [-n/2, n/2];
+ *   emax_n likewise with max; open_n = emax_n . emin_n
+ * the op is
+ *   T0 = g - hmax_w(hmin_w(g))   (bright runs narrower than w; >= 0)
+ *   T  = T0 >= thr ? T0 : 0
+ *   S  = min(T, open_L(hmax_3(T)))   (at least L rows long along the slant)
+ *   M > 0: R = hmax_9(open_M(hmax_9(T))); S = 0 where R > 0
+ *          (structures at least M long, lane markings and poles, are kept;
+ *          9 = RV_STREAK_REJECT_W)
+ *   den = max(1, 255 - g); out_c = max(0, I_c - (S (255 - I_c) + (den >> 1)) / den)
+ *          (the inverse of I' = I + (255 - I) a; out = in where S = 0)
+ * Normalised parameters: w = width odd in 3..15; L = min_len odd in 3..33;
+ * M = max_len 0 (off) or odd with L < M <= 97; slant -4..4 in quarter pixels
+ * of x per row; thr 1..255.  B <= 65535.  in and out may not alias.  s_out
+ * (nullable): the B x H x W plane of S.  ws: 16-byte aligned, two planes of
+ * B x H x (W rounded up to 16) bytes, four with max_len > 0. */
+#define RV_STREAK_REJECT_W 9
+size_t rv_streak_ws_bytes(int B, int H, int W, int max_len);
+int rv_streak_derain_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int pitch,
+                        int width, int min_len, int max_len, int slant, int thr, void* ws,
+                        size_t ws_bytes, uint8_t* s_out, void* stream);
+
 /* PreprocessPipeline.__call__ (src/preprocess/pipeline.py:32-45) of any
  * chain of the built-in ops, followed by the detector's LetterBox
  * (src/detect/yolo_ultralytics.py:28-35), as stream-ordered launches only:
@@ -168,31 +198,42 @@ int rv_dcp_dehaze_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, int p
 #define RV_CHAIN_CLAHE 0
 #define RV_CHAIN_MEDIAN 1
 #define RV_CHAIN_DCP 2
+#define RV_CHAIN_STREAK 4 /* kind 3 is not defined and is refused */
 #define RV_CHAIN_YCRCB 0
 #define RV_CHAIN_LAB 1
 #define RV_CHAIN_MAX_OPS 4
 /* One op in 24 bytes.  A DCP op (rv_dcp_dehaze_u8's normalised parameters)
  * keeps {kind, tq, radius, patch} in the four ints and {wq, eq} in the bytes
- * of `clip`; never fused with a neighbour, its chain runs op by op. */
+ * of `clip`; never fused with a neighbour, its chain runs op by op.  A streak
+ * op (rv_streak_derain_u8's normalised parameters) keeps {kind, thr, min_len,
+ * width} in the four ints and {max_len, slant} in the bytes of `clip`, and is
+ * a pass of its own in the same way. */
 typedef struct rv_chain_op {
-  int32_t kind; /* RV_CHAIN_CLAHE / RV_CHAIN_MEDIAN / RV_CHAIN_DCP */
+  int32_t kind; /* RV_CHAIN_CLAHE / RV_CHAIN_MEDIAN / RV_CHAIN_DCP / RV_CHAIN_STREAK */
   union {
     int32_t space; /* CLAHE: RV_CHAIN_YCRCB / RV_CHAIN_LAB */
     int32_t tq;    /* DCP: 1..255 */
+    int32_t thr;   /* streak: 1..255 */
   };
   union {
     int32_t tiles;  /* CLAHE: grid, 2..64 */
     int32_t radius; /* DCP: 0..64 */
+    int32_t min_len; /* streak: odd, 3..33 */
   };
   union {
     int32_t k;     /* median: 3, 5, 7 or 9 */
     int32_t patch; /* DCP: odd, 3..31 */
+    int32_t width; /* streak: odd, 3..15 */
   };
   union {
     double clip; /* CLAHE: clipLimit */
     struct {
       int32_t wq; /* DCP: 1..256 */
       int32_t eq; /* DCP: 1..2^20 */
+    };
+    struct {
+      int32_t max_len; /* streak: 0, or odd in min_len + 2..97 */
+      int32_t slant;   /* streak: -4..4 */
     };
   };
 } rv_chain_op;
@@ -225,7 +266,8 @@ int rv_preprocess_chain_route(const rv_chain_desc* desc, int H, int W, const int
 /* Workspace bytes for B frames of H x W with `pitch` bytes per row: the gate's
  * 2*B ints + B flags, the largest op's LUTs, and one scratch batch
  * (B*H*pitch) when the chain runs as two or more passes, and
- * rv_dcp_ws_bytes of the largest radius when it holds a DCP op.  0 for a bad
+ * rv_dcp_ws_bytes of the largest radius when it holds a DCP op, and
+ * rv_streak_ws_bytes of the largest max_len when it holds a streak op.  0 for a bad
  * descriptor or shape (and when nothing is needed). */
 size_t rv_preprocess_chain_ws_bytes(const rv_chain_desc* desc, int B, int H, int W, int pitch);
 /* in -> out (proc) and, when lb_out and geo are both given, the letterbox

@@ -8,6 +8,7 @@
 // HBM layout: frames are B x H x pitch bytes (interleaved BGR).
 #include "clahe.h"
 #include "dehaze.h"
+#include "derain.h"
 
 namespace rv {
 
@@ -132,27 +133,39 @@ static int check_frames(const uint8_t* in, const void* out, int B, int H, int W,
 }
 
 // ---------------------------------------------------------------------------
-// The two runners: the only code that picks a CLAHE / median / DCP launch.
+// The two runners: the only code that picks a CLAHE / median / DCP / streak
+// launch.
 // ---------------------------------------------------------------------------
 namespace {
 
 static_assert(kYCrCb == RV_CHAIN_YCRCB && kLab == RV_CHAIN_LAB, "ChainPass::space");
 
-enum PassKind { kPassClahe = 0, kPassMedian = 1, kPassClaheMedian = 2, kPassDcp = 3 };
+enum PassKind {
+  kPassClahe = 0,
+  kPassMedian = 1,
+  kPassClaheMedian = 2,
+  kPassDcp = 3,
+  kPassStreak = 4
+};
 
 // kPassClaheMedian: CLAHE(YCrCb) + median where clahe_median_fuses.
 struct ChainPass {
   int kind, space, tiles, k;
   double clip;
   DcpParams dcp;  // kPassDcp only
+  StreakParams streak;  // kPassStreak only
 };
 
 // One pass src -> dst (flags: nullptr, or the gate's per-frame flags: frames
-// it passed through are skipped).
-void launch_pass(const ChainPass& q, const uint8_t* src, uint8_t* dst, uint8_t* lut, void* dcp_ws,
+// it passed through are skipped).  op_ws: the workspace of a DCP or streak pass.
+void launch_pass(const ChainPass& q, const uint8_t* src, uint8_t* dst, uint8_t* lut, void* op_ws,
                  int B, int H, int W, int pitch, const int* flags, hipStream_t s) {
   if (q.kind == kPassDcp) {
-    launch_dcp(src, dst, B, H, W, pitch, q.dcp, dcp_ws, nullptr, nullptr, flags, s);
+    launch_dcp(src, dst, B, H, W, pitch, q.dcp, op_ws, nullptr, nullptr, flags, s);
+    return;
+  }
+  if (q.kind == kPassStreak) {
+    launch_streak(src, dst, B, H, W, pitch, q.streak, op_ws, nullptr, flags, s);
     return;
   }
   if (q.kind == kPassMedian) {
@@ -309,7 +322,8 @@ namespace {
 
 // How a descriptor runs on an H x W frame: the passes (adjacent CLAHE(YCrCb)
 // + median fused where rv_clahe_median_u8 would), the route and the
-// workspace layout [gate ints | LUTs | scratch batch | DCP workspace].
+// workspace layout [gate ints | LUTs | scratch batch | DCP workspace | streak
+// workspace].
 struct ChainPlan {
   bool identity;  // disabled or empty chain: proc = raw
   bool gate, lab;
@@ -318,6 +332,7 @@ struct ChainPlan {
   int route;
   int lut_tiles;  // largest CLAHE grid (0: no CLAHE)
   int dcp_radius;  // largest refine radius of a DCP pass (-1: no DCP)
+  int streak_max_len;  // largest max_len of a streak pass (-1: no streak pass)
 };
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -345,6 +360,11 @@ int check_desc(const rv_chain_desc* d) {
       snprintf(what, sizeof(what), "chain op %d: DCP", i);
       const int st = dcp_check(DcpParams{o.patch, o.wq, o.tq, o.radius, o.eq}, 0, 0, what);
       if (st) return st;
+    } else if (o.kind == RV_CHAIN_STREAK) {
+      char what[32];
+      snprintf(what, sizeof(what), "chain op %d: streak", i);
+      const int st = streak_check(StreakParams{o.width, o.min_len, o.max_len, o.slant, o.thr}, what);
+      if (st) return st;
     } else {
       RV_CHECK_ARG(false, "chain op %d: unknown kind %d", i, o.kind);
     }
@@ -360,6 +380,7 @@ void make_plan(const rv_chain_desc& d, int H, int W, const LbGeo* G, ChainPlan& 
   p.n = 0;
   p.lut_tiles = 0;
   p.dcp_radius = -1;
+  p.streak_max_len = -1;
   p.route = RV_CHAIN_ROUTE_OPS;
   if (p.identity) return;
   for (int i = 0; i < d.n_ops;) {
@@ -368,6 +389,13 @@ void make_plan(const rv_chain_desc& d, int H, int W, const LbGeo* G, ChainPlan& 
     if (o.kind == RV_CHAIN_DCP) {  // a pass of its own: never fused with a neighbour
       q = ChainPass{kPassDcp, 0, 0, 0, 0.0, DcpParams{o.patch, o.wq, o.tq, o.radius, o.eq}};
       p.dcp_radius = max(p.dcp_radius, o.radius);
+      ++i;
+      continue;
+    }
+    if (o.kind == RV_CHAIN_STREAK) {  // likewise a pass of its own
+      q = ChainPass{kPassStreak, 0, 0, 0, 0.0, DcpParams{},
+                    StreakParams{o.width, o.min_len, o.max_len, o.slant, o.thr}};
+      p.streak_max_len = max(p.streak_max_len, o.max_len);
       ++i;
       continue;
     }
@@ -394,8 +422,8 @@ void make_plan(const rv_chain_desc& d, int H, int W, const LbGeo* G, ChainPlan& 
 }
 
 struct ChainWs {
-  size_t gate, lut, scratch, dcp;  // byte sizes, in this order
-  size_t total() const { return gate + lut + scratch + dcp; }
+  size_t gate, lut, scratch, dcp, streak;  // byte sizes, in this order
+  size_t total() const { return gate + lut + scratch + dcp + streak; }
 };
 
 ChainWs plan_ws(const ChainPlan& p, int B, int H, int W, int pitch) {
@@ -404,6 +432,8 @@ ChainWs plan_ws(const ChainPlan& p, int B, int H, int W, int pitch) {
   w.lut = p.lut_tiles ? align256(lut_bytes(B, p.lut_tiles)) : 0;
   w.scratch = p.n >= 2 ? align256((size_t)B * H * pitch) : 0;
   w.dcp = p.dcp_radius >= 0 && B > 0 ? align256(dcp_ws_bytes(B, H, W, p.dcp_radius)) : 0;
+  w.streak =
+      p.streak_max_len >= 0 && B > 0 ? align256(streak_ws_bytes(B, H, W, p.streak_max_len)) : 0;
   return w;
 }
 
@@ -449,6 +479,8 @@ extern "C" int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, in
   if (p.dcp_radius >= 0)
     RV_CHECK_ARG((int64_t)H * W <= (1 << 24) && B <= 65535,
                  "a DCP op takes at most 65535 frames of 2^24 pixels (B=%d, %d x %d)", B, W, H);
+  if (p.streak_max_len >= 0)
+    RV_CHECK_ARG(B <= 65535, "a streak op takes at most 65535 frames (B=%d)", B);
   const ChainWs w = plan_ws(p, B, H, W, pitch);
   RV_CHECK_ARG(w.total() == 0 || (ws != nullptr && ws_bytes >= w.total()),
                "workspace too small: %zu bytes, rv_preprocess_chain_ws_bytes says %zu", ws_bytes,
@@ -487,7 +519,8 @@ extern "C" int rv_preprocess_chain_u8(const uint8_t* in, uint8_t* out, int B, in
     const uint8_t* src = in;
     for (int i = 0; i < p.n; ++i) {
       uint8_t* dst = ((p.n - 1 - i) & 1) ? scratch : out;
-      launch_pass(p.pass[i], src, dst, lut, scratch + w.scratch, B, H, W, pitch, flags, s);
+      uint8_t* op_ws = scratch + w.scratch + (p.pass[i].kind == kPassStreak ? w.dcp : 0);
+      launch_pass(p.pass[i], src, dst, lut, op_ws, B, H, W, pitch, flags, s);
       src = dst;
     }
     if (p.gate) launch_copy_frames(in, out, B, H, W, pitch, flags, s);

@@ -52,6 +52,9 @@ _SIGS = {
     "rv_dcp_dehaze_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
                                  c_void_p]),
+    "rv_streak_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "rv_streak_derain_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rv_preprocess_chain_route": (c_int, [c_void_p, c_int, c_int, POINTER(c_int)]),
     "rv_preprocess_chain_ws_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "rv_preprocess_chain_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,

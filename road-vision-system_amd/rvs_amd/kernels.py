@@ -298,6 +298,31 @@ def dcp_dehaze(frames: torch.Tensor, patch: int = 15, wq: int = 243, tq: int = 2
     return res[0] if len(res) == 1 else tuple(res)
 
 
+def streak_ws_bytes(B: int, H: int, W: int, max_len: int) -> int:
+    """Workspace bytes of rv_streak_derain_u8 (0 for a bad shape or max_len)."""
+    return int(_lib.load().rv_streak_ws_bytes(int(B), int(H), int(W), int(max_len)))
+
+
+def streak_derain(frames: torch.Tensor, width: int = 3, min_len: int = 9, max_len: int = 0,
+                  slant: int = 0, thr: int = 20, out: Optional[torch.Tensor] = None,
+                  ws: Optional[torch.Tensor] = None, s: bool = False):
+    """Directional rain-streak removal (rv_streak_derain_u8) of device frames
+    with the normalised parameters of preprocess.ops.streak_params (the
+    defaults are that function's).  Returns the frames; with s also the
+    (B, H, W) uint8 streak plane S."""
+    x, B, H, W, pitch = _frames(frames)
+    out = _like(x, out)
+    ws = _workspace(ws, streak_ws_bytes(B, H, W, max_len), x.device)
+    s_t = torch.empty((B, H, W), dtype=torch.uint8, device=x.device) if s else None
+    call("rv_streak_derain_u8", ptr(x), ptr(out), B, H, W, pitch, int(width), int(min_len),
+         int(max_len), int(slant), int(thr), ptr(ws), ws.numel(), ptr(s_t), stream_ptr())
+    single = frames.dim() != 4
+    res = out[0] if single else out
+    if s:
+        return res, (s_t[0] if single else s_t)
+    return res
+
+
 CHAIN_DESC_BYTES = 120  # sizeof(rv_chain_desc), include/rvhip.h
 CHAIN_MAX_OPS = 4
 ROUTE_FUSED, ROUTE_FUSED_GATED, ROUTE_OPS = 0, 1, 2  # RV_CHAIN_ROUTE_*
@@ -305,9 +330,10 @@ ROUTE_FUSED, ROUTE_FUSED_GATED, ROUTE_OPS = 0, 1, 2  # RV_CHAIN_ROUTE_*
 
 def chain_desc(ops, enabled: bool = True, gate_on: bool = False, contrast_thresh: float = 20.0):
     """The host descriptor (rv_chain_desc) of a preprocess chain.  ops: a list
-    of ("clahe", space, tiles, clip), ("median", k) and ("dcp", patch, wq, tq,
-    radius, eq) tuples holding the normalised parameters (preprocess.ops.
-    clahe_params / median_ksize / dcp_params).
+    of ("clahe", space, tiles, clip), ("median", k), ("dcp", patch, wq, tq,
+    radius, eq) and ("streak", width, min_len, max_len, slant, thr) tuples
+    holding the normalised parameters (preprocess.ops.clahe_params /
+    median_ksize / dcp_params / streak_params).
     Nothing is validated here: the library checks the descriptor (n_ops,
     tiles, k, ...) and answers RV_EINVAL."""
     ops = list(ops)
@@ -323,8 +349,12 @@ def chain_desc(ops, enabled: bool = True, gate_on: bool = False, contrast_thresh
         elif op[0] == "dcp":
             _, patch, wq, tq, radius, eq = op
             blob += struct.pack("<iiiiii", 2, int(tq), int(radius), int(patch), int(wq), int(eq))
+        elif op[0] == "streak":
+            _, width, min_len, max_len, slant, thr = op
+            blob += struct.pack("<iiiiii", 4, int(thr), int(min_len), int(width), int(max_len),
+                                int(slant))
         else:
-            raise ValueError(f"chain op {op[0]!r}: expected 'clahe', 'median' or 'dcp'")
+            raise ValueError(f"chain op {op[0]!r}: expected 'clahe', 'median', 'dcp' or 'streak'")
     assert len(blob) == CHAIN_DESC_BYTES
     return (ctypes.c_uint8 * CHAIN_DESC_BYTES).from_buffer_copy(blob)
 

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from .. import kernels
-from .ops import CLAHEDehaze, DarkChannelDehaze, MedianDerain, _back, _to_device
+from .ops import (CLAHEDehaze, DarkChannelDehaze, MedianDerain, StreakDerain, _back,
+                  _to_device)
 from .registry import get_op_class
 
 
@@ -54,6 +55,8 @@ class PreprocessPipeline:
                 ops.append(("median", op.k))
             elif type(op) is DarkChannelDehaze:
                 ops.append(("dcp", op.patch, op.wq, op.tq, op.radius, op.eq))
+            elif type(op) is StreakDerain:
+                ops.append(("streak", op.width, op.min_len, op.max_len, op.slant, op.thr))
             else:
                 return None, str(node.get("name"))
         if len(ops) > kernels.CHAIN_MAX_OPS:

@@ -2,7 +2,7 @@
 from typing import Dict, Type
 
 from .base import PreprocessOp
-from .ops import CLAHEDehaze, DarkChannelDehaze, MedianDerain
+from .ops import CLAHEDehaze, DarkChannelDehaze, MedianDerain, StreakDerain
 
 REGISTRY: Dict[str, Type[PreprocessOp]] = {
     "CLAHEDehaze": CLAHEDehaze,
@@ -17,6 +17,9 @@ REGISTRY: Dict[str, Type[PreprocessOp]] = {
     "DarkChannelDehaze": DarkChannelDehaze,
     "DCPDehaze": DarkChannelDehaze,
     "HIPDarkChannelDehaze": DarkChannelDehaze,
+    # no reference counterpart: the stronger derain its registry leaves room for
+    "StreakDerain": StreakDerain,
+    "HIPStreakDerain": StreakDerain,
 }
 
 
