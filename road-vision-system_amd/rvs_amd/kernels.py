@@ -112,7 +112,13 @@ def jpeg_to_bgr(records: torch.Tensor, W: int, H: int,
     """JPEG coefficient records (S, record bytes) u8 on device (what
     rv_jpeg_decode_coef and the MJPEG readers produce for W x H images; the
     records' sampling and quant tables may differ) -> (S, H, W, 3) BGR, bit
-    for bit libjpeg's default decode.  A 1-D record gives one (H, W, 3) frame."""
+    for bit libjpeg's default decode in this sense: identical to libjpeg where
+    its own builds agree (the 16-bit-safe domain, libjpeg16_safe in
+    tests/jpeg_ref.py, which every encoder output of 8-bit pixels lies in), and
+    a plain clamp beyond it.  Example: one grey block, DC only, quant entry
+    255: a quantised DC of 32 decodes to 255 everywhere; 33 (8415 * 4 leaves
+    int16) to 255 here and to 0 in libjpeg-turbo's SIMD build.
+    A 1-D record gives one (H, W, 3) frame."""
     if records.dim() == 1:
         return jpeg_to_bgr(records.unsqueeze(0), W, H,
                            None if out is None else out.unsqueeze(0))[0]

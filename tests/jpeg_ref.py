@@ -4,6 +4,11 @@ Marker parse, Huffman decode and the integer arithmetic of libjpeg's default
 decode path (islow IDCT, fancy chroma upsampling, 16-bit fixed-point
 YCbCr -> RGB), restated from the JPEG standard (ITU-T T.81) and libjpeg's
 published arithmetic.  Slow and plain on purpose; only for small fixtures.
+
+The way back, for the hand-built cases of tests/jpeg_cases.py: record() (the
+coefficient record of include/rvhip.h), entropy_encode() (the inverse of
+parse()'s scan loop), and the two predicates that bound the decoder's claim:
+libjpeg16_safe() (where libjpeg's own builds agree) and int32_safe().
 """
 import numpy as np
 
@@ -203,35 +208,87 @@ def parse(data):
     return dict(W=W, H=H, ncomp=nc, sampling=sampling, qt=qt, coef=coef, hv=hv)
 
 
-def _idct_1d(i, s):
-    """libjpeg jidctint (islow) butterfly over the leading axis of eight."""
+def _idct_1d(i, s, seen=None):
+    """libjpeg jidctint (islow) butterfly over the leading axis of eight.
+    `seen`, a list, collects every intermediate value (for int32_safe)."""
+    def k(x):
+        if seen is not None:
+            seen.append(x)
+        return x
     i = [x.astype(np.int64) for x in i]
-    z1 = (i[2] + i[6]) * 4433
-    t2 = z1 - i[6] * 15137
-    t3 = z1 + i[2] * 6270
-    t0 = (i[0] + i[4]) << 13
-    t1 = (i[0] - i[4]) << 13
-    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    z1 = k(k(i[2] + i[6]) * 4433)
+    t2 = k(z1 - k(i[6] * 15137))
+    t3 = k(z1 + k(i[2] * 6270))
+    t0 = k(k(i[0] + i[4]) << 13)
+    t1 = k(k(i[0] - i[4]) << 13)
+    t10, t13, t11, t12 = k(t0 + t3), k(t0 - t3), k(t1 + t2), k(t1 - t2)
     a0, a1, a2, a3 = i[7], i[5], i[3], i[1]
-    z1, z2, z3, z4 = a0 + a3, a1 + a2, a0 + a2, a1 + a3
-    z5 = (z3 + z4) * 9633
-    a0, a1, a2, a3 = a0 * 2446, a1 * 16819, a2 * 25172, a3 * 12299
-    z1, z2 = z1 * -7373, z2 * -20995
-    z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
-    a0, a1, a2, a3 = a0 + z1 + z3, a1 + z2 + z4, a2 + z2 + z3, a3 + z1 + z4
+    z1, z2, z3, z4 = k(a0 + a3), k(a1 + a2), k(a0 + a2), k(a1 + a3)
+    z5 = k(k(z3 + z4) * 9633)
+    a0, a1, a2, a3 = k(a0 * 2446), k(a1 * 16819), k(a2 * 25172), k(a3 * 12299)
+    z1, z2 = k(z1 * -7373), k(z2 * -20995)
+    z3, z4 = k(k(z3 * -16069) + z5), k(k(z4 * -3196) + z5)
+    a0, a1, a2, a3 = (k(a0 + k(z1 + z3)), k(a1 + k(z2 + z4)), k(a2 + k(z2 + z3)),
+                      k(a3 + k(z1 + z4)))
     out = [t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3]
-    return [(o + (1 << (s - 1))) >> s for o in out]
+    return [k(k(o) + (1 << (s - 1))) >> s for o in out]
+
+
+def idct_samples(coef, q, seen=None):
+    """(..., 64) quantised coefficients -> (..., 8, 8) samples [v, u] before
+    the clamp to 0..255."""
+    coef = np.asarray(coef)
+    d = (coef.astype(np.int64) * np.asarray(q).astype(np.int64)).reshape(coef.shape[:-1] + (8, 8))
+    if seen is not None:
+        seen.append(d)
+    cols = _idct_1d([d[..., v, :] for v in range(8)], 11, seen)  # down each column
+    ws = np.stack(cols, axis=-2)                                 # (..., v, u)
+    rows = _idct_1d([ws[..., :, u] for u in range(8)], 18, seen)  # along each row
+    return np.stack(rows, axis=-1) + 128
 
 
 def idct_plane(coef, q):
     """(bh, bw, 64) quantised coefficients -> (8 bh, 8 bw) u8 samples."""
     bh, bw, _ = coef.shape
-    d = (coef.astype(np.int64) * q.astype(np.int64)).reshape(bh, bw, 8, 8)
-    cols = _idct_1d([d[:, :, v, :] for v in range(8)], 11)       # down each column
-    ws = np.stack(cols, axis=2)                                  # (bh, bw, v, u)
-    rows = _idct_1d([ws[:, :, :, u] for u in range(8)], 18)      # along each row
-    px = np.clip(np.stack(rows, axis=3) + 128, 0, 255)
+    px = np.clip(idct_samples(coef, q), 0, 255)
     return px.transpose(0, 2, 1, 3).reshape(8 * bh, 8 * bw).astype(np.int64)
+
+
+def _fits(x, bits):
+    lim = 1 << (bits - 1)
+    x = np.asarray(x)
+    return ((x >= -lim) & (x < lim)).reshape(x.shape[0], -1).all(axis=1)
+
+
+def libjpeg16_safe(coef, q):
+    """Per block of (..., 64) coefficients: does it stay where every libjpeg
+    build decodes the same samples as a plain clamp?  libjpeg-turbo's SIMD
+    islow IDCT keeps 16-bit lanes for the dequantised coefficients, for the
+    sums it forms before widening (in0 +- in4, in7 + in3, in5 + in1, in both
+    passes) and for the workspace between the passes; the C build wraps out of
+    range samples through a mask table.  Inside these bounds they all agree."""
+    coef = np.asarray(coef)
+    c = coef.reshape(-1, 64).astype(np.int64)
+    d = (c * np.asarray(q).astype(np.int64).reshape(1, 64)).reshape(-1, 8, 8)
+    ok = _fits(d, 16)
+    ws = np.stack(_idct_1d([d[:, v, :] for v in range(8)], 11), axis=1)
+    ok &= _fits(ws, 16)
+    for i in ([d[:, v, :] for v in range(8)], [ws[:, :, u] for u in range(8)]):
+        for x in (i[0] + i[4], i[0] - i[4], i[7] + i[3], i[5] + i[1]):
+            ok &= _fits(x, 16)
+    return ok.reshape(coef.shape[:-1])
+
+
+def int32_safe(coef, q):
+    """Per block: does every intermediate of the restatement (products, sums,
+    the rounding add) fit int32?  The kernel computes in int."""
+    coef = np.asarray(coef)
+    seen = []
+    idct_samples(coef.reshape(-1, 64), q, seen)
+    ok = np.ones(coef.reshape(-1, 64).shape[0], bool)
+    for x in seen:
+        ok &= _fits(x, 32)
+    return ok.reshape(coef.shape[:-1])
 
 
 def _up_h2v1(p):
@@ -257,8 +314,9 @@ def _up_h2v2(p):
     return out
 
 
-def to_rgb(j):
-    """parse() output -> (H, W, 3) RGB u8."""
+def full_planes(j):
+    """parse() output -> the components as (H, W) int64 planes at full
+    resolution: IDCT, clamp, crop, chroma upsampling."""
     W, H = j["W"], j["H"]
     hmax, vmax = j["hv"][0]
     planes = []
@@ -273,14 +331,133 @@ def to_rgb(j):
         elif (fh, fv) == (2, 2):
             p = _up_h2v2(p)
         planes.append(p[:H, :W])
-    if len(planes) == 1:
-        return np.repeat(planes[0][:, :, None], 3, axis=2).astype(np.uint8)
-    y, cb, cr = planes[0], planes[1] - 128, planes[2] - 128
+    return planes
+
+
+def ycc_to_rgb_unclamped(y, cb, cr):
+    """(..., 3) int64 R, G, B of libjpeg's 16-bit fixed-point conversion,
+    before the clamp to 0..255."""
+    cb, cr = cb - 128, cr - 128
     r = y + ((91881 * cr + 32768) >> 16)
     g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
     b = y + ((116130 * cb + 32768) >> 16)
-    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+    return np.stack([r, g, b], axis=-1)
+
+
+def to_rgb(j):
+    """parse() output -> (H, W, 3) RGB u8."""
+    planes = full_planes(j)
+    if len(planes) == 1:
+        return np.repeat(planes[0][:, :, None], 3, axis=2).astype(np.uint8)
+    return np.clip(ycc_to_rgb_unclamped(*planes), 0, 255).astype(np.uint8)
 
 
 def decode_rgb(data):
     return to_rgb(parse(data))
+
+
+# ---- the way back: coefficient records and the entropy coder --------------
+
+RECORD_MAGIC = 0x46434A52  # "RJCF", include/rvhip.h
+
+
+def record(j):
+    """parse() output -> the coefficient record of include/rvhip.h as a u8
+    array: int32[8] {magic, W, H, sampling, ncomp, 0, 0, 0}, u16 quant tables
+    in natural order, then per component its int16 block grid."""
+    nc = len(j["coef"])
+    parts = [np.array([RECORD_MAGIC, j["W"], j["H"], j["sampling"], nc, 0, 0, 0], "<i4").view(np.uint8),
+             np.ascontiguousarray(j["qt"], "<u2").reshape(-1).view(np.uint8)]
+    assert parts[1].size == nc * 128
+    parts += [np.ascontiguousarray(c, "<i2").reshape(-1).view(np.uint8) for c in j["coef"]]
+    return np.concatenate(parts)
+
+
+def _huff_enc(counts, symbols):
+    """{symbol: (code, length)} of a canonical Huffman table."""
+    return {sym: (code, length) for (length, code), sym in _huff_table(counts, symbols).items()}
+
+
+_ENC_DC = (_huff_enc(*STD_DC_LUMA), _huff_enc(*STD_DC_CHROMA))
+_ENC_AC = (_huff_enc(*STD_AC_LUMA), _huff_enc(*STD_AC_CHROMA))
+
+
+def _value_bits(v):
+    """(size category, the category's value bits) of a coefficient (T.81 F.1.2)."""
+    s = abs(v).bit_length()
+    return s, (v if v >= 0 else v - 1) & ((1 << s) - 1)
+
+
+def block_code(blk, pred, t):
+    """(bits as an int, bit count) of one block in natural order, coded with
+    the Annex K tables of class t (0 luma, 1 chroma) after DC prediction pred."""
+    s, vb = _value_bits(int(blk[0]) - pred)
+    assert s <= 11, "DC difference without a baseline code"
+    code, n = _ENC_DC[t][s]
+    acc, bits = (code << s) | vb, n + s
+    run = 0
+    for v in blk[ZIGZAG[1:]].tolist():
+        if v == 0:
+            run += 1
+            continue
+        while run >= 16:
+            code, n = _ENC_AC[t][0xF0]
+            acc, bits = (acc << n) | code, bits + n
+            run -= 16
+        s, vb = _value_bits(v)
+        assert s <= 10, "AC coefficient without a baseline code"
+        code, n = _ENC_AC[t][(run << 4) | s]
+        acc, bits = (acc << (n + s)) | (code << s) | vb, bits + n + s
+        run = 0
+    if run:
+        code, n = _ENC_AC[t][0]
+        acc, bits = (acc << n) | code, bits + n
+    return acc, bits
+
+
+def scan_order(j, rows_per_restart=1):
+    """The blocks of the interleaved scan as [(component, by, bx)], one list
+    per restart segment of rows_per_restart MCU rows (0: a single segment)."""
+    hv = j["hv"]
+    my, mx = j["coef"][0].shape[0] // hv[0][1], j["coef"][0].shape[1] // hv[0][0]
+    rows = []
+    for yy in range(my):
+        row = []
+        for xx in range(mx):
+            for c, (h, v) in enumerate(hv):
+                row += [(c, yy * v + k // h, xx * h + k % h) for k in range(h * v)]
+        rows.append(row)
+    n = rows_per_restart or my
+    return [sum(rows[k:k + n], []) for k in range(0, my, n)]
+
+
+def encode_segment(j, blocks):
+    """One restart segment (a scan_order() list) -> (its bytes before stuffing,
+    padded with 1-bits to a whole byte; the bit count of every block)."""
+    acc, total, counts, pred = 0, 0, [], [0] * len(j["coef"])
+    for c, by, bx in blocks:
+        blk = j["coef"][c][by, bx]
+        a, n = block_code(blk, pred[c], 0 if c == 0 else 1)
+        pred[c] = int(blk[0])
+        acc, total = (acc << n) | a, total + n
+        counts.append(n)
+    pad = -total % 8
+    acc = (acc << pad) | ((1 << pad) - 1)
+    return acc.to_bytes((total + pad) // 8, "big"), counts
+
+
+def entropy_encode(j, rows_per_restart=1):
+    """The inverse of parse()'s scan loop: parse() output -> (the bytes that
+    follow the SOS header up to and including EOI, per restart segment a dict
+    {block_bits, raw_bytes, stuffed_bytes, raw}).  Annex K tables, MCU order
+    with the dummy blocks as stored, DC prediction reset per segment, 1-bit
+    padding, 0x00 after every 0xFF, RSTm between segments."""
+    out, info = bytearray(), []
+    segs = scan_order(j, rows_per_restart)
+    for k, blocks in enumerate(segs):
+        raw, counts = encode_segment(j, blocks)
+        stuffed = raw.replace(b"\xff", b"\xff\x00")
+        out += stuffed
+        out += bytes([0xFF, 0xD0 + (k & 7) if k + 1 < len(segs) else 0xD9])
+        info.append(dict(block_bits=counts, raw_bytes=len(raw), stuffed_bytes=len(stuffed), raw=raw))
+    return bytes(out), info
